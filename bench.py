@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """P-DivGNN training throughput on MI355X: mesh-nodes/sec (fwd+bwd), 1..8 GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up --config's batch, runs W warm-up and K timed steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (float32; same
+arguments, same inputs: meshes and weights are seeded), so two builds can be compared output for
+output: a training step's nmse / total (/ div) losses, its skip flag, its flat gradient (grad) and
+the parameters after its Adam update (params); the inference config's local_stress and total.
+--full adds everything else below (CPU baselines, sub-results, the published sweep).
 
 One process per GPU.  Launched without a torch.distributed launcher (no WORLD_SIZE in the
 environment), ``--gpus N`` > 1 spawns the N ranks itself (torch.multiprocessing "spawn",
@@ -19,7 +26,7 @@ Main line (the driver's metric): BASELINE.json configs[1] = 8 synthetic periodic
 71x71 meshes (5,041 nodes, 29,968 edges each) PER GPU (weak scaling, graph-level DP).
 value = nodes processed by all ranks / max-over-ranks wall time of the K timed steps.
 
-Sub-results in the same JSON line ("sub_results"; skipped with --no-extras), each timed the
+Sub-results in the same JSON line ("sub_results"; with --full, skipped with --no-extras), each timed the
 same way (barrier + synchronize on both sides, max over ranks):
   config3  P-DivGNN with the divergence loss, 32 x 5,041-node meshes per GPU (weak)
   config4  hyperelastic-style hole plates, FIXED global batch of 64 graphs sharded over the
@@ -27,8 +34,9 @@ same way (barrier + synchronize on both sides, max over ranks):
   config5  inference, one 100,489-node mesh per GPU, 15 MP layers (N independent replicas)
 
 Also reported: the roofline of the dominant kernel (HIP events around its launches inside the
-timed region) and the reference algorithm's CPU path (the op-for-op oracle restatement) timed
-on this host's cores (rank 0, N = 1 only).  --plumbing runs the launch / rendezvous / timing /
+timed region) and, with --full, the reference algorithm's CPU path (the op-for-op oracle
+restatement) timed on this host's cores (rank 0, N = 1 only) and the reference's published
+forward sweep.  --plumbing runs the launch / rendezvous / timing /
 reporting flow with a gradient-bucket all-reduce as the only work (CPU tests with gloo); its
 line says so and carries no throughput claim.
 """
@@ -461,9 +469,10 @@ def per_rank_fields(world: int, device, pg, counts, step_ms: float, allreduce_ms
             "node_balance": round(max(nodes) / (sum(nodes) / world), 4) if sum(nodes) else None}
 
 
-def time_config(cid: int, args, rank: int, world: int, pg, device) -> tuple[dict, list]:
+def time_config(cid: int, args, rank: int, world: int, pg, device, dump: bool = False) -> tuple[dict, list, dict]:
     """Build this rank's batch of config `cid`, run W warm-up and K timed steps, return the
-    record (value over all ranks, ms/step, rooflines) and this rank's samples."""
+    record (value over all ranks, ms/step, rooflines), this rank's samples and, with `dump`,
+    what the last timed step computed as host float32 arrays (last_step_outputs)."""
     from gnn_local_stress.models import EncodeProcessDecode
     from pdg.plan import plan_for
     from pdg.trainer import Trainer
@@ -488,7 +497,8 @@ def time_config(cid: int, args, rank: int, world: int, pg, device) -> tuple[dict
     if infer:
         def run_step():
             with torch.no_grad():
-                return {"total": model(batch, scale_output=True).local_stress.abs().mean()}
+                y = model(batch, scale_output=True).local_stress
+                return {"total": y.abs().mean(), "local_stress": y}
     else:
         # the global minibatch's graph count (every rank's losses are / B_global, pdg/trainer.py)
         n_global = cfg["graphs"] if cfg.get("global_batch") else cfg["graphs"] * world
@@ -578,9 +588,30 @@ def time_config(cid: int, args, rank: int, world: int, pg, device) -> tuple[dict
         "mfma_busy_source": (f"profiles/{Path(sq_path).name}" if sq_path else sq_reason),
         "kernel_ms": {k: round(v * 1e3, 4) for k, v in kt.items()},
     }
+    outputs = last_step_outputs(out, trainer, infer) if dump else {}
     del trainer, model, batch, plan
     torch.cuda.empty_cache()
-    return rec, samples
+    return rec, samples, outputs
+
+
+def last_step_outputs(out: dict, trainer, infer: bool) -> dict:
+    """What a caller of the timed path holds after the last timed step, as host float32 arrays:
+    the step's returned device values (the loss scalars and the skip flag of a training step, the
+    predicted local stress of an inference forward) and, for a training step, what it left in the
+    trainer: the flat gradient of that step and the parameters after its Adam update."""
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    if not infer:
+        arrays.update(grad=trainer.flat_g, params=trainer.flat_p)
+    return {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+
+
+def write_outputs(dirname: str, outputs: dict, rank: int, world: int) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array (every rank's as <name>_rank<r>.npy when N > 1)."""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(d / (name + (f"_rank{rank}" if world > 1 else "") + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # BASELINE.md §1: the reference's only published timings (docs/benchmark_hyperelast.svg, made by
@@ -761,6 +792,11 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--dp-mode", default="replica", choices=["replica", "sync"])
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the config 3/4/5 sub-results and the published-workload sweep "
+                         "(a plain run times --config only); the --no-* options below take parts of it away")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step of --config computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="main line only (no config 3/4/5 sub-results)")
     ap.add_argument("--extra-steps", type=int, default=10, help="timed steps of each sub-result")
@@ -816,12 +852,14 @@ def main():
         res = time_plumbing(args, rank, world, pg, device)
         subs = {}
     else:
-        res, samples = time_config(args.config, args, rank, world, pg, device)
+        res, samples, outputs = time_config(args.config, args, rank, world, pg, device, dump=bool(args.dump_outputs))
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, outputs, rank, world)
         subs = {}
-        if args.config == 2 and not args.no_extras:
+        if args.full and args.config == 2 and not args.no_extras:
             sub_args = argparse.Namespace(**{**vars(args), "steps": args.extra_steps})
             for cid in (3, 4, 5):
-                r, s = time_config(cid, sub_args, rank, world, pg, device)
+                r, s, _ = time_config(cid, sub_args, rank, world, pg, device)
                 subs[f"config{cid}"] = (r, s)
     if rank == 0:
         line = {"metric": res["metric"], "value": res["value"], "unit": res["unit"], "n_gpus": res["n_gpus"],
@@ -831,7 +869,7 @@ def main():
                 "world_size_rccl": dist.get_world_size() if pg is not None else 1,
                 "backend": backend if pg is not None else None}
         line.update({k: v for k, v in res.items() if k not in line})
-        cpu_ok = world == 1 and not args.no_cpu_baseline and not args.plumbing
+        cpu_ok = args.full and world == 1 and not args.no_cpu_baseline and not args.plumbing
         line["tree"] = tree_hash()
         line["pmc_tree"] = pmc_tree()
         line["traffic_tree_match"] = line["pmc_tree"] == line["tree"]

@@ -12,7 +12,7 @@ if [ "$K" != "-" ]; then
     > "$O/tests.log" 2>&1 || { tail -30 "$O/tests.log"; exit 1; }
   tail -1 "$O/tests.log"
 fi
-timeout -k 10 300 python bench.py --no-cpu-baseline > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$O/bench.log" 2>&1 || { tail -20 "$O/bench.log"; exit 1; }
 python - "$O/bench.log" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -51,7 +51,7 @@ if [ "$WHAT" = measure ]; then
   bash tools/sq_pass.sh "$TAG/sq" > "$O/sq_pass.log" 2>&1 || { tail -5 "$O/sq_pass.log"; exit 1; }
   cp "$R/gpurun_out/$TAG/sq/sq.txt" "$R/profiles/${ROUND:-r05}_sq.txt"
   cp "$R/gpurun_out/$TAG/sq/sq.json" "$R/profiles/${ROUND:-r05}_sq.json"
-  step bench 500 python bench.py || exit 1
+  step bench 500 python bench.py --full || exit 1
   grep '^{' "$O/bench.log" | tail -1 > "$O/bench_line.json"
   python -c "import json; d = json.load(open('$O/bench_line.json')); print(d['value'], d['ms_per_step'], d['tree'], d['traffic_tree_match'], d['roofline'])"
 fi

@@ -45,7 +45,7 @@ case "$WHAT" in
     python tools/gap_window.py "$O/prof/bench_kernel_trace.csv" --steps 12 --skip 3 --json "$O/gaps.json" > "$O/gaps.txt"
     grep '^{' "$O/prof.log" | tail -1 > "$O/prof_bench_line.json"
     rm -f "$O"/prof/*kernel_trace.csv "$O"/prof/*.db
-    step bench 600 python bench.py || exit 1
+    step bench 600 python bench.py --full || exit 1
     grep '^{' "$O/bench.log" | tail -1 > "$O/bench_line.json"
     python -c "import json; d = json.load(open('$O/bench_line.json')); print(d['value'], d['ms_per_step'], d['tree'], d['traffic_tree_match'], d['roofline']['frac'], d['roofline']['frac_pmc'])" ;;
 esac

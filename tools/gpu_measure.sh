@@ -25,7 +25,7 @@ if [ "$WHAT" = all ] || [ "$WHAT" = tests ]; then
   step pytest_gpu 1150 python -u -m pytest tests -m gpu -x -v --timeout 1100 --timeout-method thread || exit 1
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
-  step bench2 600 python bench.py || exit 1
+  step bench2 600 python bench.py --full || exit 1
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = prof ]; then
   cd /tmp && export TMPDIR=/tmp
