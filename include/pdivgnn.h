@@ -532,6 +532,38 @@ typedef struct pdg_copy_job {
  * jobs (njobs <= 65535, the largest count max_count) in one launch. */
 int pdg_collate(const pdg_copy_job* jobs, int njobs, long max_count, void* stream);
 
+/* Graph plan on the device (pdg_plan.hip): what pdg/plan.py builds with torch.sort / bincount /
+ * searchsorted, without a host read.  Every array is device memory; scratch holds
+ * pdg_graph_plan_scratch_bytes(n_nodes, n_edges, nnz) bytes (one allocation serves both calls;
+ * < 0 for n_nodes <= 0, a negative count, n_edges or nnz >= 2^31, or n_nodes + 1024 >= 2^31).
+ *
+ * pdg_graph_plan: edge_src / edge_dst are the two int64 rows of edge_index, in any order, with
+ * duplicates, self-loops and isolated nodes.  perm / src / dst (n_edges): the edges in stable
+ * (dst, src) order, perm the original edge id; rowptr_dst (n_nodes + 1) over that order;
+ * perm_src (n_edges): the stable (src, dst) order of those sorted edges; rowptr_src (n_nodes + 1).
+ * *status (device int) is cleared, then set to 1 when an endpoint lies outside [0, n_nodes); such
+ * an endpoint counts as node 0, so the outputs are a valid in-range plan either way.  The edge
+ * arrays may be NULL when n_edges == 0.
+ *
+ * pdg_div_plan: the COO divergence operator (rows / cols int64, vals fp32, nnz entries in any
+ * order) of a batch whose graph g owns the nodes ptr[g] .. ptr[g + 1] (ptr: n_graphs + 1 int32).
+ * An entry of row r belongs to the graph g with ptr[g] <= r < ptr[g + 1] and is kept when
+ * col < 2 N_g (gnn_train.py:74).  a_rowptr (n_nodes + 1) / a_col / a_val: the kept entries by row,
+ * in entry order, graph-local columns; at_rowptr (n_nodes + 1) / at_row / at_comp / at_val: the
+ * same entries by global node ptr[g] + (col mod N_g), at_comp = col >= N_g.  The entry arrays hold
+ * nnz elements, of which the first a_rowptr[n_nodes] (= at_rowptr[n_nodes], the kept count) are
+ * written; values are copied bit for bit.  An entry with a row outside [0, n_nodes), a negative
+ * column or a node outside [0, n_nodes) sets *status and is dropped.  clear_status != 0 clears
+ * *status first; 0 keeps what pdg_graph_plan left there. */
+long pdg_graph_plan_scratch_bytes(int n_nodes, long n_edges, long nnz);
+int pdg_graph_plan(int n_nodes, long n_edges, const int64_t* edge_src, const int64_t* edge_dst, int* perm,
+                   int* src, int* dst, int* rowptr_dst, int* perm_src, int* rowptr_src, int* status,
+                   void* scratch, long scratch_bytes, void* stream);
+int pdg_div_plan(int n_nodes, int n_graphs, const int* ptr, long nnz, const int64_t* rows, const int64_t* cols,
+                 const float* vals, int* a_rowptr, int* a_col, float* a_val, int* at_rowptr, int* at_row,
+                 int* at_comp, float* at_val, int* status, int clear_status, void* scratch, long scratch_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

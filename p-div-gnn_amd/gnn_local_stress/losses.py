@@ -73,7 +73,10 @@ class _SinglePlan:
             op = op.coalesce()
             idx = op.indices().to(device)
             p.has_div = True
-            GraphPlan._build_div(p, idx[0], idx[1], op.values().to(device).float())
+            if torch.device(device).type == "cuda":   # the device planner (clamped; the status word is not read)
+                p._build_div_device(idx[0], idx[1], op.values())
+            else:
+                GraphPlan._build_div(p, idx[0], idx[1], op.values().to(device).float())
         return p
 
 

@@ -230,12 +230,25 @@ class EncodeProcessDecode(StressFieldBaseModel):
                 or self.output_nodes_features_size != 3:
             raise ValueError("HIP path supports the reference feature sizes (6 node, 1 edge, 3 outputs)")
         ms = mesh_graph.mean_stress
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        # [0] the zero-stress guard, [1] the status word of a plan built here (pdg/plan.py): a graph
+        # seen for the first time is planned on the device before the guard is read, so both arrive
+        # in the one host read the reference's torch.any also has (models.py:294-299)
+        flag = torch.zeros(2, dtype=torch.int32, device=dev)
         from pdg.lib import lib, stream_handle
+        plan = plan_for(mesh_graph, status=flag[1:])
         lib.pdg_any_nonzero(ms.data_ptr(), ms.numel(), flag.data_ptr(), stream_handle(dev))
-        if not bool(flag.item()):   # models.py:294-299 (same host sync as the reference's torch.any)
+        nonzero, status = flag.tolist()
+        if not plan._checked:
+            if plan.status.data_ptr() == flag[1:].data_ptr():
+                try:
+                    plan.check_status(status)
+                except AssertionError:
+                    mesh_graph.__dict__.pop("_plan_cache", None)   # the next call plans, and raises, again
+                    raise
+            else:   # planned elsewhere and never validated (its status word is its own)
+                plan.validate()
+        if not nonzero:
             return Data(local_stress=torch.zeros_like(ms), edge_index=mesh_graph.edge_index, pos=mesh_graph.pos)
-        plan = plan_for(mesh_graph)
         ops.register_plan(mesh_graph.edge_index, plan)
         params = [self.get_parameter(n) for n in PARAM_NAMES]
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)

@@ -55,6 +55,7 @@ class DeviceGraphStore:
                 rows, cols = op.indices()[0], op.indices()[1]
                 vals = op.values()
             plans.append(GraphPlan(d.edge_index.to(dev), d.num_nodes, None, rows, cols, vals))
+            plans[-1].validate()   # construction synchronises anyway; batches assembled from these are in range
         self.has_div = all(p.has_div for p in plans)
         self.nnz = np.array([p.a_col.numel() if self.has_div else 0 for p in plans], dtype=np.int64)
         self.nnzt = np.array([p.at_row.numel() if self.has_div else 0 for p in plans], dtype=np.int64)

@@ -38,6 +38,7 @@ class CapturedForward:
         self.model = model
         self.device = dev
         self.plan = plan_for(graph)
+        self.plan.validate()   # construction synchronises anyway; replays never read the status word
         self.eng = model._engine_for(dev)
         self.params = [model.get_parameter(n).detach() for n in PARAM_NAMES]
         self.P = dict(zip(PARAM_NAMES, self.params))
