@@ -564,6 +564,46 @@ int pdg_div_plan(int n_nodes, int n_graphs, const int* ptr, long nnz, const int6
                  int* at_comp, float* at_val, int* status, int clear_status, void* scratch, long scratch_bytes,
                  void* stream);
 
+/* Per-node fields of a bare triangle mesh on the device (pdg_meshfields.hip): the last host step of
+ * the reference's convert_mesh_to_graph (benchmark_gnn_fem.py:388-415) and the operator of the
+ * divergence check, with no host-side topology work.  points: (n_nodes, dim) fp32, dim 2 or 3 (only
+ * x and y are used); faces: (n_faces, 3) int64 (may be NULL when n_faces == 0).  scratch holds
+ * pdg_mesh_fields_scratch_bytes(n_nodes, n_faces) bytes (host arithmetic; one size serves both calls;
+ * < 0 for n_nodes <= 0, n_faces < 0, n_nodes + 1024 >= 2^31 or 9 n_faces + 1024 >= 2^31).  Sizes, null
+ * pointers, the scratch size and the capacity are checked on the host before any HIP call.  Kernel
+ * launches only (no memset or copy node, no cooperative launch); the results do not depend on the
+ * order in which the kernels' atomics land.
+ *
+ * pdg_node_labels: compute_node_labels (datasets.py:122-179).  A boundary edge is an undirected edge
+ * of exactly one face (extract_feature_edges(boundary_edges=True)); a boundary node an endpoint of
+ * one; the boundary nodes are grouped into connected components over the boundary edges.  A component
+ * is external (labels +1) when one of its nodes lies on the bounding box: x equal to the smallest or
+ * largest x, or y equal to the smallest or largest y, compared exactly in fp32 against the min / max
+ * of the same array.  (The reference tests `coord in bounds_2d` over all four bounds, so it would
+ * also accept x == ymin; comparing each coordinate with its own bounds only is deliberate.)  Every
+ * other component is an internal boundary (-1); interior nodes and nodes of no face get 0.
+ * info (3 device ints): info[0] = boundary components, info[1] = external ones, info[2] = status bits:
+ *   1  a face holds an index outside [0, n_nodes): the face is ignored, the index never dereferenced;
+ *   2  a boundary node has other than two boundary edges (non-manifold boundary; labels still written);
+ *   4  the component search stopped at its iteration cap (boundary edges + 2 passes; never on a search
+ *      that works as designed, since a pass moves a component's smallest id one edge further).
+ *
+ * pdg_p1_div_operator: the area-averaged P1 nodal divergence operator A = [Dx | Dy] (n_nodes x
+ * 2 n_nodes) of pdg/meshgen.py p1_divergence_operator (the role of op_div_matrix, datasets.py:191-213):
+ * per face det = (xb-xa)(yc-ya) - (xc-xa)(yb-ya), area = |det| / 2 and the P1 gradients gx, gy; row i
+ * (a vertex of the face) receives area gx[vn] at column vn and area gy[vn] at column vn + n_nodes for
+ * each vertex vn, divided by the node's summed incident area.  Output: COO sorted by (row, col),
+ * duplicates summed, structural zeros kept (every key the host keeps); *nnz (device int) entries of
+ * the `capacity` >= 18 n_faces provided.  Sums are fp64 in face-index order, rounded once to fp32.
+ * *status (device int) bits: 1 a face has det == 0 (its contributions are skipped; the host function
+ * divides by zero there), 2 a face index is out of range (the face is ignored). */
+long pdg_mesh_fields_scratch_bytes(int n_nodes, int n_faces);
+int pdg_node_labels(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                    int64_t* labels, int* info, void* scratch, long scratch_bytes, void* stream);
+int pdg_p1_div_operator(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                        int64_t* rows, int64_t* cols, float* vals, long capacity, int* nnz, int* status,
+                        void* scratch, long scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 // reported as *n_edges = -1.
 #include <cfloat>
 
+#include "pdg_bbox.hpp"     // bbox_kernel, bbox_load
 #include "pdg_common.hpp"
 #include "pdg_runtime.hpp"
 #include "pdg_scan.hpp"   // scan_local / scan_blocks / scan_add kernels and scan()
@@ -54,38 +55,7 @@ struct Scratch {
   int* nb;         // [6F + pairs] slot array: 2 * col + (1 if periodic else 0)
 };
 
-constexpr int BBOX_BLOCKS = 256;
-
 __device__ __forceinline__ float nmul(float a, float b) { return __fmul_rn(a, b); }
-
-__global__ __launch_bounds__(GT) void bbox_kernel(int n, const float* __restrict__ p, int dim, float* __restrict__ part,
-                                                  int* __restrict__ ctr) {
-  __shared__ float red[4][GT];
-  float mnx = FLT_MAX, mny = FLT_MAX, mxx = -FLT_MAX, mxy = -FLT_MAX;
-  for (int i = blockIdx.x * GT + threadIdx.x; i < n; i += gridDim.x * GT) {
-    const float x = p[(size_t)i * dim], y = p[(size_t)i * dim + 1];
-    mnx = fminf(mnx, x);
-    mny = fminf(mny, y);
-    mxx = fmaxf(mxx, x);
-    mxy = fmaxf(mxy, y);
-  }
-  red[0][threadIdx.x] = mnx;
-  red[1][threadIdx.x] = mny;
-  red[2][threadIdx.x] = mxx;
-  red[3][threadIdx.x] = mxy;
-  __syncthreads();
-  for (int s = GT / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      red[0][threadIdx.x] = fminf(red[0][threadIdx.x], red[0][threadIdx.x + s]);
-      red[1][threadIdx.x] = fminf(red[1][threadIdx.x], red[1][threadIdx.x + s]);
-      red[2][threadIdx.x] = fmaxf(red[2][threadIdx.x], red[2][threadIdx.x + s]);
-      red[3][threadIdx.x] = fmaxf(red[3][threadIdx.x], red[3][threadIdx.x + s]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) part[4 * blockIdx.x + threadIdx.x] = red[threadIdx.x][0];
-  if (blockIdx.x == 0 && threadIdx.x < 16) ctr[threadIdx.x] = 0;
-}
 
 // Side membership (exact float equality, as the reference's ==), compaction into the 4
 // side lists (left, right, lower, upper: the concatenation order of datasets.py:85-100)
@@ -94,12 +64,7 @@ __global__ __launch_bounds__(GT) void sides_kernel(int n, const float* __restric
                                                    const float* __restrict__ part, int nparts, int* __restrict__ ctr,
                                                    int* __restrict__ side) {
   __shared__ float bb[4];
-  if (threadIdx.x < 4) {
-    float v = part[threadIdx.x];
-    for (int b = 1; b < nparts; ++b) v = threadIdx.x < 2 ? fminf(v, part[4 * b + threadIdx.x]) : fmaxf(v, part[4 * b + threadIdx.x]);
-    bb[threadIdx.x] = v;
-  }
-  __syncthreads();
+  bbox_load(part, nparts, bb);
   const float mnx = bb[0], mny = bb[1], mxx = bb[2], mxy = bb[3];
   for (int i = blockIdx.x * GT + threadIdx.x; i < n; i += gridDim.x * GT) {
     const float x = p[(size_t)i * dim], y = p[(size_t)i * dim + 1];
@@ -355,8 +320,8 @@ extern "C" int pdg_mesh_graph(int n_nodes, const float* points, int dim, int n_f
   hipStream_t st = (hipStream_t)stream;
   Scratch s;
   layout(n_nodes, n_faces, &s, (char*)scratch);
-  const int nbb = (int)std::min<long>(BBOX_BLOCKS, (n_nodes + GT - 1) / GT);
-  hipLaunchKernelGGL(bbox_kernel, dim3(nbb), dim3(GT), 0, st, n_nodes, points, dim, s.bbox, s.ctr);
+  const int nbb = bbox_blocks(n_nodes);
+  hipLaunchKernelGGL(bbox_kernel, dim3(nbb), dim3(BBOX_T), 0, st, n_nodes, points, dim, s.bbox, s.ctr);
   if (periodic) {
     hipLaunchKernelGGL(sides_kernel, dim3(grid_for(n_nodes)), dim3(GT), 0, st, n_nodes, points, dim, s.bbox, nbb,
                        s.ctr, s.side);

@@ -1,5 +1,5 @@
 // Exclusive prefix sum of an int32 array on the device, shared by the CSR builders
-// (pdg_graph.hip, pdg_plan.hip).  Included once per translation unit; everything lives in an
+// (pdg_graph.hip, pdg_plan.hip, pdg_meshfields.hip).  Included once per translation unit; everything lives in an
 // unnamed namespace, so each unit carries its own copy of the three kernels.
 #pragma once
 #include <hip/hip_runtime.h>

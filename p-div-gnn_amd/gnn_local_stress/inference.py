@@ -58,6 +58,37 @@ def predict_and_save(model: models.EncodeProcessDecode, dataloader: DataLoader, 
 
 
 @torch.no_grad()
+def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic: bool = True,
+                 divergence: bool = False):
+    """The reference's published workload (``scripts/benchmark_gnn_fem.py:388-415`` then one
+    forward) from a bare mesh: ``mesh`` is a legacy-VTK path or a ``(points, faces)`` pair of
+    arrays / tensors, ``mean_stress`` the imposed mean field (3 values).  The graph, the node
+    labels and the forward (``scale_output=True``) run on the model's device; no ``.npz`` is
+    needed.  Returns the graph ``Data`` with ``local_stress`` (the prediction) and
+    ``nodes_types``; with ``divergence`` returns ``(data, div)``, ``div`` the prediction's
+    divergence penalty (``losses.compute_divergence`` with the mesh's P1 operator, which is
+    kept as ``data.op_div_matrix``).  Triangle meshes only."""
+    from pdg.devgraph import convert_mesh_to_graph
+    from . import losses, vtk_io
+    if isinstance(mesh, (str, Path)):
+        points, faces = vtk_io.read_legacy_vtk(mesh)
+    else:
+        points, faces = mesh
+    device = next(model.parameters()).device
+    points = torch.as_tensor(points).to(device=device, dtype=torch.float32)
+    faces = torch.as_tensor(faces).to(device=device, dtype=torch.int64)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"predict_mesh takes triangle meshes only (faces of shape (F, 3)), got "
+                         f"{tuple(faces.shape)}: quad meshes are not built on the device")
+    data = convert_mesh_to_graph(points, faces, mean_stress, None, periodic, divergence)
+    data.local_stress = model.forward(data, scale_output=True, scale_input=True).local_stress
+    if not divergence:
+        return data
+    div = losses.compute_divergence(data.local_stress, data.op_div_matrix, data.surfaces_nodes_for_div)
+    return data, div
+
+
+@torch.no_grad()
 def run_inference(dataset_csv, results_folder, model_weights_path, periodic_graph: bool, batch_size: int,
                   latent_size: int, message_passing_steps: int, device, config_path=None) -> None:
     """gnn_inference.py:84-138."""

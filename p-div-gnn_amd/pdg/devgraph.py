@@ -51,16 +51,95 @@ def mesh_graph(points: torch.Tensor, faces: torch.Tensor, periodic: bool = True)
     return ei[:, :e].contiguous(), ea[:e].clone()
 
 
-def convert_mesh_to_graph(points: torch.Tensor, faces: torch.Tensor, mean_stress, node_labels: torch.Tensor,
-                          periodic: bool = True) -> Data:
+def _mesh_tensors(points: torch.Tensor, faces: torch.Tensor, what: str):
+    if points.device.type != "cuda" or faces.device.type != "cuda":
+        raise RuntimeError(f"{what} needs device tensors (the HIP path has no CPU fallback)")
+    pts = points.contiguous().float()
+    fcs = faces.contiguous().to(torch.int64)
+    if pts.dim() != 2 or pts.shape[1] not in (2, 3) or fcs.dim() != 2 or (fcs.shape[0] and fcs.shape[1] != 3):
+        raise ValueError("points must be (N, 2|3) and faces (F, 3): triangle meshes only")
+    nbytes = lib.pdg_mesh_fields_scratch_bytes(pts.shape[0], fcs.shape[0])
+    if nbytes < 0:
+        raise ValueError("empty mesh, or a mesh beyond int32 indexing")
+    return pts, fcs, torch.empty(nbytes, dtype=torch.uint8, device=pts.device), nbytes
+
+
+def node_labels(points: torch.Tensor, faces: torch.Tensor, strict: bool = True) -> torch.Tensor:
+    """``compute_node_labels`` (``datasets.py:122-179``) on the device (``pdg_node_labels``,
+    csrc/pdg_meshfields.hip): (N,) int64 with +1 on the external boundary, -1 on an internal
+    boundary (a hole's rim) and 0 elsewhere; bitwise ``pdg.meshgen.node_labels``.  One host
+    read (the three status words).  Raises ValueError for a face index outside the mesh and for
+    a boundary that is not a set of closed curves (a boundary node with other than two boundary
+    edges); with ``strict`` also unless the mesh has exactly two boundaries, one of them
+    external -- the reference's "Expected 2 regions" assertion.  ``strict=False`` labels a
+    plate with any number of holes, none included."""
+    pts, fcs, scratch, nbytes = _mesh_tensors(points, faces, "node_labels")
+    n, dim = pts.shape
+    nf = fcs.shape[0]
+    dev = pts.device
+    labels = torch.empty(n, dtype=torch.int64, device=dev)
+    info = torch.empty(3, dtype=torch.int32, device=dev)
+    lib.pdg_node_labels(n, pts.data_ptr(), dim, nf, fcs.data_ptr() if nf else None, labels.data_ptr(),
+                        info.data_ptr(), scratch.data_ptr(), nbytes, stream_handle(dev))
+    ncomp, next_, status = info.tolist()
+    if status & 1:
+        raise ValueError(f"faces hold a node index outside [0, {n})")
+    if status & 2:
+        raise ValueError("non-manifold boundary: a boundary node has other than two boundary edges")
+    if status & 4:
+        raise RuntimeError("pdg_node_labels: the boundary component search did not converge")
+    if strict and (ncomp != 2 or next_ != 1):
+        raise ValueError(f"Expected 2 regions (one external, one internal boundary), found {ncomp} "
+                         f"({next_} external); strict=False labels any number of holes")
+    return labels
+
+
+_labels_of = node_labels   # convert_mesh_to_graph's `node_labels` argument shadows the function
+
+
+def p1_divergence(points: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """The area-averaged P1 divergence operator A = [Dx | Dy] of a triangle mesh as a coalesced
+    sparse COO (N, 2N) float32 tensor on the device (``pdg_p1_div_operator``): rows and columns
+    bitwise ``pdg.meshgen.p1_divergence_operator``'s, values to one float32 rounding of the same
+    fp64 sums.  One host read (entry count and status).  Raises ValueError for a face index
+    outside the mesh or a face of zero area."""
+    pts, fcs, scratch, nbytes = _mesh_tensors(points, faces, "p1_divergence")
+    n, dim = pts.shape
+    nf = fcs.shape[0]
+    dev = pts.device
+    cap = 18 * nf
+    idx = torch.empty(2, max(cap, 1), dtype=torch.int64, device=dev)
+    vals = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+    cnt = torch.empty(2, dtype=torch.int32, device=dev)
+    lib.pdg_p1_div_operator(n, pts.data_ptr(), dim, nf, fcs.data_ptr() if nf else None, idx[0].data_ptr(),
+                            idx[1].data_ptr(), vals.data_ptr(), cap, cnt.data_ptr(), cnt[1:].data_ptr(),
+                            scratch.data_ptr(), nbytes, stream_handle(dev))
+    nnz, status = cnt.tolist()
+    if status & 2:
+        raise ValueError(f"faces hold a node index outside [0, {n})")
+    if status & 1:
+        raise ValueError("a face has zero area: the P1 gradients are undefined there")
+    return torch.sparse_coo_tensor(idx[:, :nnz], vals[:nnz], (n, 2 * n), is_coalesced=True)
+
+
+def convert_mesh_to_graph(points: torch.Tensor, faces: torch.Tensor, mean_stress,
+                          node_labels: torch.Tensor | None = None, periodic: bool = True,
+                          divergence: bool = False) -> Data:
     """``benchmark_gnn_fem.py:388-415`` on the device: the graph of one FEM sample, ready for
     ``EncodeProcessDecode`` (pos reduced to (x, y) float32, mean stress broadcast to every
-    node, node labels as both ``surfaces_nodes_for_div`` and ``nodes_types``)."""
+    node, node labels as both ``surfaces_nodes_for_div`` and ``nodes_types``).  Without
+    ``node_labels`` they are computed from the mesh on the device (``node_labels`` above,
+    strict); ``divergence`` also sets ``op_div_matrix`` (``p1_divergence``)."""
     edge_index, edge_attr = mesh_graph(points, faces, periodic)
     n = points.shape[0]
     dev = points.device
+    if node_labels is None:
+        node_labels = _labels_of(points, faces)
     labels = node_labels.to(dev).reshape(-1, 1).to(torch.int64)
     ms = torch.as_tensor(mean_stress, dtype=torch.float32, device=dev).reshape(1, 3)
-    return Data(edge_index=edge_index, edge_attr=edge_attr, pos=points[:, :2].float().contiguous(),
-                face=faces.T.contiguous(), mean_stress=torch.ones(n, 3, device=dev) * ms,
-                surfaces_nodes_for_div=labels, nodes_types=labels.clone(), is_periodic=periodic)
+    out = Data(edge_index=edge_index, edge_attr=edge_attr, pos=points[:, :2].float().contiguous(),
+               face=faces.T.contiguous(), mean_stress=torch.ones(n, 3, device=dev) * ms,
+               surfaces_nodes_for_div=labels, nodes_types=labels.clone(), is_periodic=periodic)
+    if divergence:
+        out.op_div_matrix = p1_divergence(points, faces)
+    return out

@@ -110,9 +110,12 @@ SIGNATURES: dict[str, list] = {
     "pdg_graph_plan_scratch_bytes": [I, ctypes.c_long, ctypes.c_long],
     "pdg_graph_plan": [I, ctypes.c_long] + [P] * 10 + [ctypes.c_long, P],
     "pdg_div_plan": [I, I, P, ctypes.c_long] + [P] * 11 + [I, P, ctypes.c_long, P],
+    "pdg_mesh_fields_scratch_bytes": [I, I],
+    "pdg_node_labels": [I, P, I, I, P, P, P, P, ctypes.c_long, P],
+    "pdg_p1_div_operator": [I, P, I, I, P, P, P, P, ctypes.c_long, P, P, P, ctypes.c_long, P],
 }
 _RESTYPES = {"pdg_last_error": ctypes.c_char_p, "pdg_source_hash": ctypes.c_char_p, "pdg_mesh_graph_scratch_bytes": ctypes.c_long,
-             "pdg_graph_plan_scratch_bytes": ctypes.c_long}
+             "pdg_graph_plan_scratch_bytes": ctypes.c_long, "pdg_mesh_fields_scratch_bytes": ctypes.c_long}
 
 LN_STAT_BYTES = 40   # sizeof(pdg_ln_stat)
 # PDG_DEBUG_SYNC=1: synchronise after every library call and name it on stderr (locating a faulting kernel)

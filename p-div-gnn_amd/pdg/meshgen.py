@@ -171,6 +171,44 @@ def p1_divergence_operator(pos: np.ndarray, faces: np.ndarray):
     return (uniq // (2 * n)).astype(np.int64), (uniq % (2 * n)).astype(np.int64), acc.astype(np.float32)
 
 
+def node_labels(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, int, int]:
+    """``compute_node_labels`` (``datasets.py:122-179``) from the mesh alone: (labels (N,) int64,
+    boundary components, external ones).  A boundary edge belongs to exactly one face; the
+    boundary nodes (its endpoints) are grouped into connected components over those edges
+    (union-find); a component with a node on the bounding box -- x equal to min / max x or y
+    equal to min / max y, exactly, in float32 -- is the external boundary (+1), every other one
+    an internal boundary (-1); all other nodes are 0.  The host restatement of
+    ``pdg_node_labels`` (csrc/pdg_meshfields.hip); ``hole_plate`` labels its own square plate
+    by another rule, so the two check each other."""
+    p = np.asarray(pos, dtype=np.float32)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    n = len(p)
+    labels = np.zeros(n, np.int64)
+    fe = np.sort(np.concatenate([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]], 0), 1)
+    ue, cnt = np.unique(fe, axis=0, return_counts=True) if len(fe) else (fe, np.zeros(0, np.int64))
+    be = ue[cnt == 1]
+    parent = np.arange(n)
+
+    def find(a: int) -> int:
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for u, v in be:
+        ru, rv = find(int(u)), find(int(v))
+        if ru != rv:
+            parent[max(ru, rv)] = min(ru, rv)
+    bnodes = np.unique(be.ravel())
+    roots = np.array([find(int(b)) for b in bnodes], np.int64)
+    on_box = ((p[:, 0] == p[:, 0].min()) | (p[:, 0] == p[:, 0].max())
+              | (p[:, 1] == p[:, 1].min()) | (p[:, 1] == p[:, 1].max()))
+    external = set(roots[on_box[bnodes]].tolist())
+    for b, r in zip(bnodes, roots):
+        labels[b] = NODE_EXTERNAL_BOUNDARY if int(r) in external else NODE_INTERNAL_BOUNDARY
+    return labels, len(set(roots.tolist())), len(external)
+
+
 def hole_plate(n: int = 71, hole_radius: float = 0.0, length: float = 100.0,
                jitter: float = 0.15, periodic: bool = True, seed: int = 69,
                stress_scale: float = 100.0, strain_range: tuple[float, float] | None = None) -> MeshSample:
