@@ -479,6 +479,45 @@ int pdg_div_bwd(int n_graphs, const int* ptr, int n_nodes, const int* at_rowptr,
                 const int* at_comp, const float* at_val, const float* div, const float* scale,
                 int reduce_abs, int accumulate, float* g_sigma, void* stream);
 
+/* ---------------------------------------------------------------- evaluation metrics */
+/* The numbers of scripts/compare_results.py (main, lines 1098-1245), one workgroup per graph over
+ * the node segments ptr[0..B], fp64 sums in a fixed order, kernel launches only (no memset, nothing
+ * allocated: both calls can be captured).  A graph's values depend on its own rows and their position
+ * inside the graph only, so it scores bitwise the same alone and inside any batch.  A graph without
+ * nodes (ptr[g] == ptr[g+1]) gets NaN in its table row and no field row; nothing past row N of a
+ * field is written.  n_graphs <= 0, a NULL ptr, table or required input (and std == 0) are refused on
+ * the host before any launch.
+ *
+ * pdg_eval_nmse replaces normalized_mse_loss_single(reduce=False / True) (compare_results.py:333-348),
+ * normalized_mse_loss_element_wise (:351-364), von_mises_stress (:713-726) and sklearn's r2_score as
+ * main calls it (:1166-1204).  gt, pred: (N, 3) fp32 in xx, yy, xy order; every mean, difference and
+ * square is formed in fp64 from them.  table: (B, 6) fp64 =
+ *   nmse_xx, nmse_yy, nmse_xy   sum (gt - pred)^2 / sum (gt - mean gt)^2 per component,
+ *   nmse                        the mean of the three,
+ *   nmse_vm                     the same ratio on vm = sqrt(0.5 ((x-y)^2 + x^2 + y^2 + 6 xy^2)),
+ *   r2                          1 - nmse: sklearn's r2_score(gt, pred) with uniform averaging whenever
+ *                               the denominators are non-zero.  sklearn's special case for a zero
+ *                               denominator (a constant gt column scores 0 or 1) is NOT reproduced:
+ *                               a zero denominator gives the IEEE quotient (inf or NaN), as numpy does.
+ * Optional outputs (each may be NULL), fp32 rounded once from fp64: err_field (N, 4; 16-byte aligned) =
+ * (gt - pred)^2 / den_c for the three components and for von Mises; vm_gt, vm_pred (N). */
+int pdg_eval_nmse(int n_graphs, const int* ptr, const float* gt, const float* pred, double* table,
+                  float* err_field, float* vm_gt, float* vm_pred, void* stream);
+/* pdg_eval_div replaces compute_divergence (compare_results.py:647-673) on a field and on its
+ * standardised image (data_utils.standardize, compare_results.py:1081-1084, :1152-1155) and
+ * compute_divergence_norm_field (:122-141) on both.  The operator is pdg_div_fwd's: CSR over global
+ * rows with graph-local columns (col < n_g: x block; entries at or beyond 2 n_g are ignored).  One
+ * walk over a row's entries forms div[v] = A_v . [[sxx;sxy],[sxy;syy]] on sigma and on
+ * (sigma - mean) / std, each entry standardised, multiplied and summed in fp64 (the second is not the
+ * first over std: the operator's row sums are not zero on boundary rows).  table: (B, 2) fp64 = the
+ * divergence scalar of the raw and of the standardised field: rows with node_type +-1 zeroed,
+ * |.| (reduce_abs) or the square, the mean over all n_g rows, summed over the two components.
+ * norm, norm_std (N, each may be NULL): sqrt(dx^2 + dy^2) of the raw / standardised field with only
+ * the node_type == +1 rows zeroed, fp32 rounded once. */
+int pdg_eval_div(int n_graphs, const int* ptr, const int* a_rowptr, const int* a_col, const float* a_val,
+                 const int64_t* node_types, const float* sigma, float mean, float std, int reduce_abs,
+                 double* table, float* norm, float* norm_std, void* stream);
+
 /* ---------------------------------------------------------------- utilities */
 /* out (cols x rows, contiguous) = in^T for a (rows x cols) row-major matrix with row stride ld. */
 int pdg_transpose(int rows, int cols, int ld, const float* in, float* out, void* stream);
