@@ -29,10 +29,19 @@ from dataclasses import dataclass, field
 import torch
 
 from . import hiptimer
-from .lib import LN_BWD_BYTES, LN_STAT_BYTES, lib, stream_handle
+from .lib import LN_STAT_BYTES, lib, stream_handle
+from .lib import ptr as _p
 from .plan import GraphPlan
 
 L = 128
+VP, IA = ctypes.c_void_p, ctypes.c_int
+
+
+def _arr(ctype, values):
+    """A ctypes array argument (pointer tables, row counts, leading dimensions) of a batched entry point."""
+    values = list(values)
+    return (ctype * len(values))(*values)
+
 
 PARAM_SHAPES = [  # state_dict order of gnn_local_stress/models.py:246-286
     ("node_encoder.0.weight", (L, 6)), ("node_encoder.0.bias", (L,)),
@@ -53,53 +62,37 @@ PARAM_SHAPES = [  # state_dict order of gnn_local_stress/models.py:246-286
 PARAM_NAMES = [n for n, _ in PARAM_SHAPES]
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 # Kernel variants of the engine: attribute -> (A/B environment variable, shipped default).  The
 # defaults are the product path, the only one the full-size parity tests (tests/test_gpu_fullsize.py)
-# and the bench time; the alternatives are kept for same-box A/B timing (tools/ab_env.sh) and are
-# checked against the defaults by the GPU op / model tests.  Tests select them through the engine
-# attributes; the environment is read only under PDG_AB=1, and a non-default value set in the
+# and the bench time; the alternatives are kept for same-box A/B timing (tools/ab_env.sh).  The rule:
+# a boolean variant has a branch in the engine only while a GPU model test runs that branch against the
+# default (tests/test_gpu_model.py) and tests/test_gpu_engine_launches.py pins its launch sequence; an
+# A/B that is settled leaves the engine (its figures stay in EXPERIMENTS.md, its baseline kernel in the
+# library, callable through the C ABI and compared by the op tests).  Tests select variants through the
+# engine attributes; the environment is read only under PDG_AB=1, and a non-default value set in the
 # environment without it is an error (a stray variable must not swap kernels silently).
 VARIANTS = {
     # edge backward with the W2 / Wc weight gradients fused (pdg_edge_bwd_w2 / pdg_edge_gout_wc); False:
     # pdg_edge_bwd + deferred pdg_wgrad_segments passes
     "fused_edge_wgrad": ("PDG_FUSED_EDGE_WGRAD", True),
-    # P/Q gather backward before the Wc pass (gz1m / gz1e re-read while still in the Infinity Cache:
-    # pq_scatter_bwd 63.6 -> 59.7 us and edge_gout_wc 145 -> 140 us per call, same box)
-    "pq_first": ("PDG_PQ_FIRST", True),
     # fused edge backward: gz1e not stored; the P/Q gather backward forms it per row as gC - gz1m (one fp32
     # rounding of |gC|) from the gC rows the Wc pass reads anyway: one E-row array written fewer per step
     "gz1e_from_gc": ("PDG_GZ1E_FROM_GC", True),
     # edge forward in the block-cooperative layout (pdg_edge_fwd_coop; 240 -> 230 us per call at config 2)
     # instead of pdg_edge_fwd
     "coop_fwd": ("PDG_EDGE_FWD_COOP", True),
-    # inference (no backward): the edge forward of at least INFER_PIPE_MIN_EDGES edges in 16-row rounds with one
-    # barrier per round (pdg_edge_fwd_infer; bitwise the same rows): 494 -> 446 us per 614k-edge call
-    "fwd_infer_pipe": ("PDG_EDGE_FWD_INFER", True),
-    # the backward's input gradient of x (gP, gQ -> gx) in bf16x6 (pdg_gemm_sum2_coop) instead of the fp32-MFMA
-    # pdg_gemm_sum2_rw
-    "gsum2_coop": ("PDG_GSUM2_COOP", True),
-    # node_net backward likewise (pdg_node_bwd_coop, three W^T products in bf16x6), and the cooperative
-    # node-encoder / decoder backward
-    "nbwd_coop": ("PDG_NODE_BWD_COOP", True),
     # pdg_wgrad_pairs blocks per CU (2 per CU ran as two sequential block waves at 166 VGPRs: 9.07-9.12 vs
     # 9.14-9.23 ms per config-2 step, same box)
     "pair_blocks_per_cu": ("PDG_PAIR_BLOCKS_PER_CU", 1),
-    # the node encoder in the cooperative layout with an unbiased bf16x6 W2 product (pdg_node_enc_fwd) instead of
-    # the LDS-weight fp32-MFMA pdg_encoder_fwd
-    "node_enc_coop": ("PDG_NODE_ENC_COOP", True),
-    # the decoder likewise (pdg_decoder_fwd_coop) instead of the LDS-weight pdg_decoder_fwd[_fin]
-    "decoder_coop": ("PDG_DECODER_COOP", True),
     # pdg_edge_enc_fwd blocks per CU (104 VGPRs, 41 KB LDS per 8-wave block)
     "enc_blocks_per_cu": ("PDG_ENC_BLOCKS_PER_CU", 2),
 }
 
 
-# pdg_edge_fwd_infer from this many edges on (alone, 256 blocks: +1.5 us against pdg_edge_fwd_coop at 2.5k - 11k
-# edges, equal at 27k, -3 us at 59k, -10 % from 150k edges on; tools/diag/efwd_sweep.py)
+# inference (no backward): pdg_edge_fwd_infer (16-row rounds with one barrier per round, bitwise the rows of
+# pdg_edge_fwd_coop: 494 -> 446 us per 614k-edge call) from this many edges on (alone, 256 blocks: +1.5 us
+# against pdg_edge_fwd_coop at 2.5k - 11k edges, equal at 27k, -3 us at 59k, -10 % from 150k edges on;
+# tools/diag/efwd_sweep.py)
 INFER_PIPE_MIN_EDGES = 32768
 
 
@@ -172,6 +165,85 @@ class FwdCtx:
     stats: _StatBuf = None
 
 
+@dataclass
+class _Fwd:
+    """What one phase of the forward hands the next."""
+    s: int                      # stream handle
+    ctx: FwdCtx
+    need_grad: bool
+    # the LayerNorm whose output, plus the residual x / e, is the next step's (or the decoder's) x / e:
+    # (its input a2, pointer to its statistics, its weight, its bias); the encoder's before step 0
+    ln_n: tuple = None
+    ln_e: tuple = None
+    x: torch.Tensor = None      # x_{t-1} / e_{t-1}, the residuals (None before step 0)
+    e: torch.Tensor = None
+    # node LayerNorm statistics not reduced yet: pend_n block partials in pend_buf, reduced inside their
+    # consumer (the next node_pq, the decoder); None: finalized already (sync mode)
+    pend_n: int = None
+    pend_buf: torch.Tensor = None
+    Pm: torch.Tensor = None     # P = Wa x_t, Q = Wb x_t (PQm: both in the blocked layout, pdg_pq_layout)
+    Qm: torch.Tensor = None
+    PQm: torch.Tensor = None
+
+
+@dataclass
+class _Bwd:
+    """What one phase of the backward hands the next."""
+    s: int                      # stream handle
+    G: dict                     # name -> fp32 gradient accumulator
+    T: dict                     # W^T copies (EPDEngine.transposed)
+    S: int                      # message-passing steps
+    fused: bool                 # fused_edge_wgrad
+    e_sum: bool                 # gz1e never stored: pdg_pq_scatter_bwd takes gC - gz1m
+    # LayerNorm backward without finalize launches (include/pdivgnn.h, pdg_ln_colsum): every column-sum
+    # producer adds its per-block rows into its group's accumulator (accs: node_net, edge_net, node encoder,
+    # edge encoder) and writes per-block (S1, S2) pairs into its row of `pairs`, which the consumer reduces
+    accs: tuple
+    pairs: torch.Tensor
+    slabs_w2: torch.Tensor = None   # weight-gradient slabs of the fused edge backward, over all steps
+    slabs_wc: torch.Tensor = None
+    slabs_ee: torch.Tensor = None
+    # deferred weight gradients: per weight block the (G, X, rows) segments of every step
+    segs: dict = field(default_factory=lambda: {k: [] for k in ("W2", "Wc", "Wa", "Wb", "Wn2", "Wn1a", "Wn1b",
+                                                                 "d1", "ne2", "ee2")})
+    reds: list = field(default_factory=list)         # slab reductions left to pdg_bwd_epilogue
+    epi_narrow: list = field(default_factory=list)   # narrow weight-gradient finalizes for pdg_bwd_epilogue
+    epi_enc: tuple = None                            # the edge encoder's first-layer sums, likewise
+    # the input-gradient chain, step to step
+    gx_next: torch.Tensor = None    # d loss / d x_{t+1}
+    gx_t: torch.Tensor = None       # the buffer d loss / d x_t is written to (swapped with gx_next)
+    ge_next: torch.Tensor = None    # d loss / d e_{t+1} (None at the last step: e_S has no consumer)
+    ge_bufs: list = None
+    gaggr: torch.Tensor = None
+    gx_part: torch.Tensor = None
+    gz1m: torch.Tensor = None
+    gz1e: torch.Tensor = None
+    gC_fused: torch.Tensor = None
+    n_node: int = 0                 # pairs in the row of the node LayerNorm whose consumer runs next
+    sync_slot: int = 0
+
+    def PN(self, t):   # pairs of step t's node / message / edge-update LayerNorm
+        return self.pairs[t]
+
+    def PM(self, t):
+        return self.pairs[self.S + t]
+
+    def PE(self, t):
+        return self.pairs[2 * self.S + t]
+
+
+# the deferred weight gradients that have no pair pass: segment key, weight, its leading dimension and first
+# column, bias
+_DEFERRED = [
+    ("W2", "processor.edge_net.2.weight", L, 0, "processor.edge_net.2.bias"),
+    ("Wc", "processor.edge_net.0.weight", 3 * L, 2 * L, "processor.edge_net.0.bias"),
+    ("Wn2", "processor.node_net.2.weight", L, 0, "processor.node_net.2.bias"),
+    ("d1", "node_decoder.0.weight", L, 0, "node_decoder.0.bias"),
+    ("ne2", "node_encoder.2.weight", L, 0, "node_encoder.2.bias"),
+    ("ee2", "edge_encoder.2.weight", L, 0, "edge_encoder.2.bias"),
+]
+
+
 class EPDEngine:
     """Stateless executor; parameters are passed per call as a name->tensor dict."""
 
@@ -179,6 +251,7 @@ class EPDEngine:
         self.device = torch.device(device)
         var = kernel_variants(variants)
         self.max_blocks = lib.pdg_max_blocks()
+        self._cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         f64 = dict(dtype=torch.float64, device=self.device)
         self._part_a = torch.empty(self.max_blocks * 2, **f64)
         self._part_b = torch.empty(self.max_blocks * 2, **f64)
@@ -186,8 +259,7 @@ class EPDEngine:
         # LayerNorm backward (no finalize launches, pdg_ln_colsum in include/pdivgnn.h): per-block
         # column accumulators of the 4 LayerNorm parameter groups (node_net, edge_net, node and edge
         # encoder), rows <= the largest producer grid (2 x CUs), zeroed once per backward
-        self._acc_rows = min(2 * torch.cuda.get_device_properties(self.device).multi_processor_count,
-                             self.max_blocks)
+        self._acc_rows = min(2 * self._cus, self.max_blocks)
         self._ln_acc = torch.zeros(4, self._acc_rows * 256, **f64)
         self._sync_pairs = torch.zeros(8, 2, **f64)
         self._part_narrow = torch.empty(self.max_blocks * (L * 6 + L + 6), **f64)
@@ -197,27 +269,22 @@ class EPDEngine:
         self._part_narrow_ne = torch.empty(self.max_blocks * (L * 6 + L + 6), **f64)
         self._nparts = ctypes.c_int(0)
         # one weight-gradient slab per block of pdg_wgrad_segments: three blocks per CU
-        self._nslabs = lib.pdg_wgrad_slabs_per_cu() * torch.cuda.get_device_properties(self.device).multi_processor_count
-        self._nslabs_p = min(var["pair_blocks_per_cu"] *
-                             torch.cuda.get_device_properties(self.device).multi_processor_count, lib.pdg_max_blocks())
+        self._nslabs = lib.pdg_wgrad_slabs_per_cu() * self._cus
+        self._nslabs_p = min(var["pair_blocks_per_cu"] * self._cus, self.max_blocks)
+        # one 8-wave block per CU: the grid of the cooperative kernels and the slabs of the fused edge backward
+        self._nslabs_e = min(self._cus, self.max_blocks)
+        self._enc_blocks = min(var["enc_blocks_per_cu"] * self._cus, self.max_blocks)
         self._pair = torch.zeros(2, **f64)
+        # slab sets of the deferred weight gradients, allocated by the first backward that needs them
+        self._slab_sets: dict = {}
+        self._slabs_p = None
         self.sync = None
-        # kernel variants (VARIANTS above; tests and A/B tools flip these attributes)
-        self.fused_edge_wgrad = var["fused_edge_wgrad"]
-        self.pq_first = var["pq_first"]
-        self.gz1e_from_gc = var["gz1e_from_gc"]
-        self.coop_fwd = var["coop_fwd"]
-        self.fwd_infer_pipe = var["fwd_infer_pipe"]
-        self.node_enc_coop = var["node_enc_coop"]
-        self.decoder_coop = var["decoder_coop"]
+        # the boolean kernel variants (VARIANTS above; tests and A/B tools flip these attributes)
+        for k, v in var.items():
+            if isinstance(v, bool):
+                setattr(self, k, v)
         # the P / Q layout the library's node pre-pass writes and its cooperative edge forward reads
         self.pq_blocked = bool(lib.pdg_pq_layout())
-        self._nslabs_e = min(torch.cuda.get_device_properties(self.device).multi_processor_count,
-                             lib.pdg_max_blocks())
-        self.gsum2_coop = var["gsum2_coop"]
-        self.nbwd_coop = var["nbwd_coop"]
-        self._enc_blocks = min(var["enc_blocks_per_cu"] *
-                               torch.cuda.get_device_properties(self.device).multi_processor_count, lib.pdg_max_blocks())
         # optional live kernel timing: name -> list of (start, end) hiptimer.Event pairs
         self.timed: dict | None = None
         # optional backward probe (tools/grad_err_stages.py): step t -> copies of d loss / d x_t,
@@ -227,8 +294,8 @@ class EPDEngine:
     def variants(self) -> dict:
         """The kernel variants in effect (recorded in the bench line): every VARIANTS entry, so a new
         variant cannot be left out of the record."""
-        cus = torch.cuda.get_device_properties(self.device).multi_processor_count
-        derived = {"pair_blocks_per_cu": self._nslabs_p // cus, "enc_blocks_per_cu": self._enc_blocks // cus}
+        derived = {"pair_blocks_per_cu": self._nslabs_p // self._cus,
+                   "enc_blocks_per_cu": self._enc_blocks // self._cus}
         return {k: derived[k] if k in derived else getattr(self, k) for k in VARIANTS}
 
     def _t(self, name: str, fn, *args):
@@ -266,47 +333,56 @@ class EPDEngine:
     # ------------------------------------------------------------------ forward
     def forward(self, P: dict, stats8: torch.Tensor, plan: GraphPlan, pos, mean_stress, nodes_types,
                 edge_attr, steps: int, scale_input: bool, scale_output: bool, need_grad: bool):
-        s = stream_handle(self.device)
         N, E = plan.n_nodes, plan.n_edges
         if N == 0:
             raise ValueError("empty graph")
+        if steps < 1:
+            raise ValueError("message_passing_steps must be >= 1")
         # E == 0 (an edgeless batch): as in the reference, every message aggregate is zero
         # (scatter of no rows), the edge branch produces empty tensors and the edge parameters get
         # zero gradients; the edge kernels are skipped
         if E == 0 and self.sync is not None:
             raise ValueError("exact (sync) data parallelism needs edges on every rank's shard")
-        np_ = ctypes.byref(self._nparts)
         ctx = FwdCtx(plan=plan, steps=steps, scale_output=scale_output)
         # without edges the edge LayerNorms' entries are never finalized (zeros keep them finite)
         ctx.stats = _StatBuf(2 + 3 * steps, LN_STAT_BYTES, self.device, zero=E == 0)
-        st = ctx.stats
+        f = _Fwd(s=stream_handle(self.device), ctx=ctx, need_grad=need_grad)
+        self._fwd_encode(P, f, stats8, pos, mean_stress, nodes_types, edge_attr, scale_input)
+        if self.pq_blocked:   # one N x 256 array, Q's blocks 16 floats after P's (pdg_pq_layout)
+            f.PQm = self._empty(N, 2 * L)
+            f.Pm, f.Qm = f.PQm, f.PQm.view(-1)[16:]
+        else:
+            f.Pm, f.Qm = self._empty(N, L), self._empty(N, L)
+        for t in range(steps):
+            self._fwd_step(P, f, t)
+        return self._fwd_decode(P, f, stats8), ctx
+
+    def _fwd_encode(self, P, f: _Fwd, stats8, pos, mean_stress, nodes_types, edge_attr, scale_input) -> None:
+        """Input formatting and the two encoders (models.py:308-309)."""
+        ctx, s, st = f.ctx, f.s, f.ctx.stats
+        N, E = ctx.plan.n_nodes, ctx.plan.n_edges
         x_in = self._empty(N, 6)
         e_in = self._empty(E)
-        lib.pdg_format_inputs(N, E, _p(pos), _p(mean_stress), _p(nodes_types), _p(edge_attr), _p(plan.perm),
+        lib.pdg_format_inputs(N, E, _p(pos), _p(mean_stress), _p(nodes_types), _p(edge_attr), _p(ctx.plan.perm),
                               _p(stats8), int(scale_input), _p(x_in), _p(e_in), s)
-        # encoders (models.py:308-309)
+        # the node encoder in the cooperative layout, one 8-wave block per CU (168 VGPRs)
         a1_ne, a2_ne = self._empty(N, L), self._empty(N, L)
-        if self.node_enc_coop:
-            nb = self._nslabs_e   # one 8-wave block per CU (168 VGPRs)
-            self._t("node_enc_fwd", lib.pdg_node_enc_fwd, N, _p(x_in), _p(P["node_encoder.0.weight"]),
-                    _p(P["node_encoder.0.bias"]), _p(P["node_encoder.2.weight"]), _p(P["node_encoder.2.bias"]),
-                    _p(a1_ne), _p(a2_ne), _p(self._part_b), nb, s)
-            self._nparts.value = nb
-        else:
-            lib.pdg_encoder_fwd(N, 6, _p(x_in), _p(P["node_encoder.0.weight"]), _p(P["node_encoder.0.bias"]),
-                                _p(P["node_encoder.2.weight"]), _p(P["node_encoder.2.bias"]), _p(a1_ne), _p(a2_ne),
-                                _p(self._part_b), np_, s)
+        nb = self._nslabs_e
+        self._t("node_enc_fwd", lib.pdg_node_enc_fwd, N, _p(x_in), _p(P["node_encoder.0.weight"]),
+                _p(P["node_encoder.0.bias"]), _p(P["node_encoder.2.weight"]), _p(P["node_encoder.2.bias"]),
+                _p(a1_ne), _p(a2_ne), _p(self._part_b), nb, s)
+        self._nparts.value = nb
         # the node encoder's LayerNorm statistics are reduced inside step 0's node_pq (pdg_node_pq_rw_fin, as
         # every later step's; one launch fewer), its partials in _part_b until then (the edge encoder and the
         # first edge forward write _part_a / _part_b only after that node_pq)
-        pend_n, pend_buf = None, self._part_b
+        f.pend_buf = self._part_b
         if self.sync is None:
-            pend_n = self._nparts.value
+            f.pend_n = nb
         else:
             self._finalize(self._part_b, N * L, st[0], s)
         # the edge encoder's layer-1 output is stored only for the unfused backward (pdg_mlp2_bwd);
         # pdg_edge_enc_bwd recomputes it from the scalar input
-        a1_ee = self._empty(E, L) if (need_grad and not self.fused_edge_wgrad) else None
+        a1_ee = self._empty(E, L) if (f.need_grad and not self.fused_edge_wgrad) else None
         a2_ee = self._empty(E, L)
         if E and a1_ee is None:   # bf16x6 W2 product, register-stationary (pdg_edge_enc_fwd)
             nb = self._enc_blocks
@@ -318,127 +394,124 @@ class EPDEngine:
         elif E:
             lib.pdg_encoder_fwd(E, 1, _p(e_in), _p(P["edge_encoder.0.weight"]), _p(P["edge_encoder.0.bias"]),
                                 _p(P["edge_encoder.2.weight"]), _p(P["edge_encoder.2.bias"]), _p(a1_ee), _p(a2_ee),
-                                _p(self._part_a), np_, s)
+                                _p(self._part_a), ctypes.byref(self._nparts), s)
             self._finalize(self._part_a, E * L, st[1], s, True)
-        if need_grad:
+        if f.need_grad:
             ctx.x_in, ctx.e_in, ctx.a1_ne, ctx.a2_ne, ctx.a1_ee, ctx.a2_ee = x_in, e_in, a1_ne, a2_ne, a1_ee, a2_ee
+        f.ln_n = (a2_ne, st[0], P["node_encoder.4.weight"], P["node_encoder.4.bias"])
+        f.ln_e = (a2_ee, st[1], P["edge_encoder.4.weight"], P["edge_encoder.4.bias"])
 
+    def _fwd_step(self, P, f: _Fwd, t: int) -> None:
+        """Message-passing step t (models.py:313-314): node pre-pass, edge_net, aggregation, node_net."""
+        ctx, s, st, need_grad = f.ctx, f.s, f.ctx.stats, f.need_grad
+        plan = ctx.plan
+        N, E = plan.n_nodes, plan.n_edges
+        i_m, i_e, i_n = 2 + 3 * t, 3 + 3 * t, 4 + 3 * t
+        ge, be = P["processor.edge_net.4.weight"], P["processor.edge_net.4.bias"]
+        gn, bnn = P["processor.node_net.4.weight"], P["processor.node_net.4.bias"]
+        a2n_prev, stn_prev, gn_prev, bn_prev = f.ln_n
+        x_t = self._empty(N, L)
+        if f.pend_n is not None:    # the previous node LayerNorm's statistics, reduced inside node_pq
+            self._t("node_pq", lib.pdg_node_pq_rw_fin, N, _p(a2n_prev), f.pend_buf.data_ptr(), f.pend_n,
+                    float(N * L), stn_prev, _p(gn_prev), _p(bn_prev), _p(f.x), _p(x_t),
+                    _p(P["processor.edge_net.0.weight"]), _p(f.Pm), _p(f.Qm), s)
+            f.pend_n = None
+        else:
+            self._t("node_pq", lib.pdg_node_pq_rw, N, _p(a2n_prev), stn_prev, _p(gn_prev), _p(bn_prev),
+                    _p(f.x), _p(x_t), _p(P["processor.edge_net.0.weight"]), _p(f.Pm), _p(f.Qm), s)
+        # the last step's edge update has no consumer (models.py:316 decodes nodes only)
+        eu = t < ctx.steps - 1
+        e_t = self._empty(E, L)
+        a2m = self._empty(E, L)
+        a1m = self._empty(E, L) if need_grad else None   # layer-1 outputs: backward only
+        a2e = self._empty(E, L) if eu else None
+        a1e = self._empty(E, L) if (eu and need_grad) else None
+        fin_in_segsum = bool(E) and self.sync is None   # edge statistics reduced inside pdg_segment_sum_fin
+        if E:
+            self._fwd_edge_net(P, f, eu, e_t, a1m, a2m, a1e, a2e)
+        if E and not fin_in_segsum:   # sync mode: all-reduced over the ranks
+            self._finalize(self._part_a, E * L, st[i_m], s, True)
+            if eu:
+                self._finalize(self._part_b, E * L, st[i_e], s, True)
+        # aggregation (models.py:215-217) and node_net (:240-243)
+        a1n = self._empty(N, L) if need_grad else None
+        a2n = self._empty(N, L)
+        if E:
+            aggr = self._empty(N, L)
+            xs = self._empty(N, L) if need_grad else None
+            if fin_in_segsum:   # + both edge LayerNorms' statistics from the edge forward's partials
+                self._t("segment_sum", lib.pdg_segment_sum_fin, N, _p(plan.rowptr_dst), _p(a2m),
+                        _p(self._part_a), _p(self._part_b) if eu else None, self._nparts.value, float(E * L),
+                        st[i_m], st[i_e] if eu else None, _p(ge), _p(be), _p(aggr), _p(xs), s)
+            else:
+                self._t("segment_sum", lib.pdg_segment_sum, N, _p(plan.rowptr_dst), _p(a2m), st[i_m], _p(ge),
+                        _p(be), _p(aggr), _p(xs), s)
+        else:
+            aggr = torch.zeros(N, L, dtype=torch.float32, device=self.device)
+            xs = torch.zeros(N, L, dtype=torch.float32, device=self.device) if need_grad else None
+        self._t("node_net", lib.pdg_node_net, N, _p(aggr), _p(x_t), _p(P["processor.node_net.0.weight"]),
+                _p(P["processor.node_net.0.bias"]), _p(P["processor.node_net.2.weight"]),
+                _p(P["processor.node_net.2.bias"]), _p(a1n), _p(a2n), _p(self._part_a),
+                ctypes.byref(self._nparts), s)
+        if self.sync is None:
+            # finalised by the next step's node_pq, or by the decoder after the last step
+            f.pend_n, f.pend_buf = self._nparts.value, self._part_a
+        else:
+            self._finalize(self._part_a, N * L, st[i_n], s)
+        if need_grad:
+            ctx.per_step.append(dict(x=x_t, e=e_t, a1m=a1m, a2m=a2m, a1e=a1e, a2e=a2e, aggr=aggr, xs=xs,
+                                     a1n=a1n, a2n=a2n, i_m=i_m, i_e=i_e, i_n=i_n, eu=eu))
+        f.ln_n = (a2n, st[i_n], gn, bnn)
+        f.ln_e = (a2e, st[i_e], ge, be)
+        f.x, f.e = x_t, e_t
+
+    def _fwd_edge_net(self, P, f: _Fwd, eu: bool, e_t, a1m, a2m, a1e, a2e) -> None:
+        """e_t and both edge_net evaluations of one step (message, and with `eu` the edge update), the
+        LayerNorm partials of a2m / a2e in _part_a / _part_b (_nparts of them)."""
+        plan, s = f.ctx.plan, f.s
+        N, E = plan.n_nodes, plan.n_edges
+        a2e_prev, ste_prev, ge_prev, be_prev = f.ln_e
         W1, b1 = P["processor.edge_net.0.weight"], P["processor.edge_net.0.bias"]
         W2, b2 = P["processor.edge_net.2.weight"], P["processor.edge_net.2.bias"]
-        ge, be = P["processor.edge_net.4.weight"], P["processor.edge_net.4.bias"]
-        Wn1, bn1 = P["processor.node_net.0.weight"], P["processor.node_net.0.bias"]
-        Wn2, bn2 = P["processor.node_net.2.weight"], P["processor.node_net.2.bias"]
-        gn, bnn = P["processor.node_net.4.weight"], P["processor.node_net.4.bias"]
+        name = "edge_fwd" if eu else "edge_fwd_last"
+        if self.coop_fwd and not f.need_grad and E >= INFER_PIPE_MIN_EDGES:
+            self._t(name, lib.pdg_edge_fwd_infer, E, _p(a2e_prev), ste_prev, _p(ge_prev), _p(be_prev), _p(f.e),
+                    _p(e_t), _p(plan.src), _p(plan.dst), _p(f.Pm), _p(f.Qm), _p(W1), _p(b1), _p(W2), _p(b2),
+                    _p(a2m), _p(a2e), _p(self._part_a), _p(self._part_b), int(eu), self._nslabs_e, s)
+            self._nparts.value = self._nslabs_e
+        elif self.coop_fwd:
+            self._t(name, lib.pdg_edge_fwd_coop, E, _p(a2e_prev), ste_prev, _p(ge_prev), _p(be_prev), _p(f.e),
+                    _p(e_t), _p(plan.src), _p(plan.dst), _p(f.Pm), _p(f.Qm), _p(W1), _p(b1), _p(W2), _p(b2),
+                    _p(a1m), _p(a2m), _p(a1e), _p(a2e), _p(self._part_a), _p(self._part_b), int(eu),
+                    self._nslabs_e, s)
+            self._nparts.value = self._nslabs_e
+        else:
+            Pu, Qu = f.Pm, f.Qm
+            if self.pq_blocked:   # pdg_edge_fwd (the A/B / reference kernel) reads two N x 128 arrays
+                v = f.PQm.view(N, 8, 2, 16)
+                Pu, Qu = v[:, :, 0].reshape(N, L).contiguous(), v[:, :, 1].reshape(N, L).contiguous()
+            self._t(name, lib.pdg_edge_fwd, E, _p(a2e_prev), ste_prev, _p(ge_prev), _p(be_prev), _p(f.e),
+                    _p(e_t), _p(plan.src), _p(plan.dst), _p(Pu), _p(Qu), _p(W1), _p(b1), _p(W2), _p(b2),
+                    _p(a1m), _p(a2m), _p(a1e), _p(a2e), _p(self._part_a), _p(self._part_b), int(eu),
+                    ctypes.byref(self._nparts), s)
 
-        a2n_prev, stn_prev, gn_prev, bn_prev = a2_ne, st[0], P["node_encoder.4.weight"], P["node_encoder.4.bias"]
-        a2e_prev, ste_prev, ge_prev, be_prev = a2_ee, st[1], P["edge_encoder.4.weight"], P["edge_encoder.4.bias"]
-        x_prev = e_prev = None
-        if self.pq_blocked:   # one N x 256 array, Q's blocks 16 floats after P's (pdg_pq_layout)
-            PQm = self._empty(N, 2 * L)
-            Pm, Qm = PQm, PQm.view(-1)[16:]
-        else:
-            Pm, Qm = self._empty(N, L), self._empty(N, L)
-        # pend_n: deferred node LayerNorm statistics (nparts of the partials in pend_buf)
-        for t in range(steps):
-            i_m, i_e, i_n = 2 + 3 * t, 3 + 3 * t, 4 + 3 * t
-            x_t = self._empty(N, L)
-            if pend_n is not None:    # the previous step's node statistics, reduced inside node_pq
-                self._t("node_pq", lib.pdg_node_pq_rw_fin, N, _p(a2n_prev), pend_buf.data_ptr(), pend_n,
-                        float(N * L), stn_prev, _p(gn_prev), _p(bn_prev), _p(x_prev), _p(x_t), _p(W1), _p(Pm),
-                        _p(Qm), s)
-                pend_n = None
-            else:
-                self._t("node_pq", lib.pdg_node_pq_rw, N, _p(a2n_prev), stn_prev, _p(gn_prev), _p(bn_prev),
-                        _p(x_prev), _p(x_t), _p(W1), _p(Pm), _p(Qm), s)
-            # the last step's edge update has no consumer (models.py:316 decodes nodes only)
-            eu = t < steps - 1
-            e_t = self._empty(E, L)
-            a2m = self._empty(E, L)
-            a1m = self._empty(E, L) if need_grad else None   # layer-1 outputs: backward only
-            a2e = self._empty(E, L) if eu else None
-            a1e = self._empty(E, L) if (eu and need_grad) else None
-            if E and self.coop_fwd and not need_grad and self.fwd_infer_pipe and E >= INFER_PIPE_MIN_EDGES:
-                self._t("edge_fwd" if eu else "edge_fwd_last", lib.pdg_edge_fwd_infer, E, _p(a2e_prev), ste_prev,
-                        _p(ge_prev), _p(be_prev), _p(e_prev), _p(e_t), _p(plan.src), _p(plan.dst), _p(Pm), _p(Qm),
-                        _p(W1), _p(b1), _p(W2), _p(b2), _p(a2m), _p(a2e), _p(self._part_a), _p(self._part_b), int(eu),
-                        self._nslabs_e, s)
-                self._nparts.value = self._nslabs_e
-            elif E and self.coop_fwd:
-                self._t("edge_fwd" if eu else "edge_fwd_last", lib.pdg_edge_fwd_coop, E, _p(a2e_prev), ste_prev,
-                        _p(ge_prev), _p(be_prev), _p(e_prev), _p(e_t), _p(plan.src), _p(plan.dst), _p(Pm), _p(Qm),
-                        _p(W1), _p(b1), _p(W2), _p(b2), _p(a1m), _p(a2m), _p(a1e), _p(a2e), _p(self._part_a),
-                        _p(self._part_b), int(eu), self._nslabs_e, s)
-                self._nparts.value = self._nslabs_e
-            elif E:
-                Pu, Qu = Pm, Qm
-                if self.pq_blocked:   # pdg_edge_fwd (the A/B / reference kernel) reads two N x 128 arrays
-                    v = PQm.view(N, 8, 2, 16)
-                    Pu, Qu = v[:, :, 0].reshape(N, L).contiguous(), v[:, :, 1].reshape(N, L).contiguous()
-                self._t("edge_fwd" if eu else "edge_fwd_last", lib.pdg_edge_fwd, E, _p(a2e_prev), ste_prev, _p(ge_prev), _p(be_prev), _p(e_prev),
-                        _p(e_t), _p(plan.src), _p(plan.dst), _p(Pu), _p(Qu), _p(W1), _p(b1), _p(W2), _p(b2),
-                        _p(a1m), _p(a2m), _p(a1e), _p(a2e), _p(self._part_a), _p(self._part_b), int(eu), np_, s)
-            fin_in_segsum = bool(E) and self.sync is None   # reduced inside pdg_segment_sum_fin
-            if E and not fin_in_segsum:
-                if eu and self.sync is None:    # both edge LayerNorms in one launch
-                    lib.pdg_ln_finalize2(self._part_a.data_ptr(), self._part_b.data_ptr(), self._nparts.value,
-                                         float(E * L), st[i_m], st[i_e], s)
-                else:
-                    self._finalize(self._part_a, E * L, st[i_m], s, True)
-                    if eu:
-                        self._finalize(self._part_b, E * L, st[i_e], s, True)
-            # aggregation (models.py:215-217) and node_net (:240-243)
-            a1n = self._empty(N, L) if need_grad else None
-            a2n = self._empty(N, L)
-            if E:
-                aggr = self._empty(N, L)
-                xs = self._empty(N, L) if need_grad else None
-                if fin_in_segsum:   # + both edge LayerNorms' statistics from the edge forward's partials
-                    self._t("segment_sum", lib.pdg_segment_sum_fin, N, _p(plan.rowptr_dst), _p(a2m),
-                            _p(self._part_a), _p(self._part_b) if eu else None, self._nparts.value, float(E * L),
-                            st[i_m], st[i_e] if eu else None, _p(ge), _p(be), _p(aggr), _p(xs), s)
-                else:
-                    self._t("segment_sum", lib.pdg_segment_sum, N, _p(plan.rowptr_dst), _p(a2m), st[i_m], _p(ge),
-                            _p(be), _p(aggr), _p(xs), s)
-            else:
-                aggr = torch.zeros(N, L, dtype=torch.float32, device=self.device)
-                xs = torch.zeros(N, L, dtype=torch.float32, device=self.device) if need_grad else None
-            self._t("node_net", lib.pdg_node_net, N, _p(aggr), _p(x_t), _p(Wn1), _p(bn1), _p(Wn2), _p(bn2), _p(a1n),
-                    _p(a2n), _p(self._part_a), np_, s)
-            if self.sync is None:
-                # finalised by the next step's node_pq, or by the decoder after the last step
-                pend_n, pend_buf = self._nparts.value, self._part_a
-            else:
-                self._finalize(self._part_a, N * L, st[i_n], s)
-            if need_grad:
-                ctx.per_step.append(dict(x=x_t, e=e_t, a1m=a1m, a2m=a2m, a1e=a1e, a2e=a2e, aggr=aggr, xs=xs,
-                                         a1n=a1n, a2n=a2n, i_m=i_m, i_e=i_e, i_n=i_n, eu=eu))
-            a2n_prev, stn_prev, gn_prev, bn_prev = a2n, st[i_n], gn, bnn
-            a2e_prev, ste_prev, ge_prev, be_prev = a2e, st[i_e], ge, be
-            x_prev, e_prev = x_t, e_t
-        # decoder (models.py:316-321)
+    def _fwd_decode(self, P, f: _Fwd, stats8):
+        """The decoder (models.py:316-321) on x_S = LN_n(a2n_{S-1}) + x_{S-1}; with pending partials the
+        last node LayerNorm's statistics are reduced inside it."""
+        ctx, s = f.ctx, f.s
+        N = ctx.plan.n_nodes
+        a2n_prev, stn_prev, gn_prev, bn_prev = f.ln_n
+        pend = f.pend_n is not None
         x_S, a1d, y = self._empty(N, L), self._empty(N, L), self._empty(N, 3)
-        if x_prev is None:
-            raise ValueError("message_passing_steps must be >= 1")
-        if self.decoder_coop:   # (pend_n: the last node LayerNorm's statistics reduced inside the decoder)
-            self._t("decoder_fwd", lib.pdg_decoder_fwd_coop, N, _p(a2n_prev), None if pend_n is not None else stn_prev,
-                    pend_buf.data_ptr() if pend_n is not None else None, pend_n or 0, float(N * L),
-                    stn_prev if pend_n is not None else None, _p(gn_prev), _p(bn_prev), _p(x_prev), _p(x_S),
-                    _p(P["node_decoder.0.weight"]), _p(P["node_decoder.0.bias"]), _p(a1d),
-                    _p(P["node_decoder.2.weight"]), _p(P["node_decoder.2.bias"]), _p(stats8), int(scale_output),
-                    _p(y), self._nslabs_e, s)
-        elif pend_n is not None:   # the last node LayerNorm's statistics reduced inside the decoder
-            lib.pdg_decoder_fwd_fin(N, _p(a2n_prev), pend_buf.data_ptr(), pend_n, float(N * L), stn_prev,
-                                    _p(gn_prev), _p(bn_prev), _p(x_prev), _p(x_S), _p(P["node_decoder.0.weight"]),
-                                    _p(P["node_decoder.0.bias"]), _p(a1d), _p(P["node_decoder.2.weight"]),
-                                    _p(P["node_decoder.2.bias"]), _p(stats8), int(scale_output), _p(y), s)
-        else:
-            lib.pdg_decoder_fwd(N, _p(a2n_prev), stn_prev, _p(gn_prev), _p(bn_prev), _p(x_prev), _p(x_S),
-                                _p(P["node_decoder.0.weight"]), _p(P["node_decoder.0.bias"]), _p(a1d),
-                                _p(P["node_decoder.2.weight"]), _p(P["node_decoder.2.bias"]), _p(stats8),
-                                int(scale_output), _p(y), s)
-        if need_grad:
+        self._t("decoder_fwd", lib.pdg_decoder_fwd_coop, N, _p(a2n_prev), None if pend else stn_prev,
+                f.pend_buf.data_ptr() if pend else None, f.pend_n or 0, float(N * L),
+                stn_prev if pend else None, _p(gn_prev), _p(bn_prev), _p(f.x), _p(x_S),
+                _p(P["node_decoder.0.weight"]), _p(P["node_decoder.0.bias"]), _p(a1d),
+                _p(P["node_decoder.2.weight"]), _p(P["node_decoder.2.bias"]), _p(stats8), int(ctx.scale_output),
+                _p(y), self._nslabs_e, s)
+        if f.need_grad:
             ctx.x_S, ctx.a1d = x_S, a1d
-        return y, ctx
+        return y
 
     # ------------------------------------------------------------------ backward
     def transposed(self, P: dict) -> dict:
@@ -461,9 +534,8 @@ class EPDEngine:
         tr("processor.node_net.0.weight", "Wn1bT", L, 2 * L)
         tr("node_encoder.2.weight", "Wne2T", 0, L)
         tr("edge_encoder.2.weight", "Wee2T", 0, L)
-        n = len(jobs)
-        lib.pdg_transpose128_batch(n, (ctypes.c_void_p * n)(*[j[0] for j in jobs]), (ctypes.c_int * n)(*[j[1] for j in jobs]),
-                                   (ctypes.c_void_p * n)(*[j[2] for j in jobs]), s)
+        lib.pdg_transpose128_batch(len(jobs), _arr(VP, (j[0] for j in jobs)), _arr(IA, (j[1] for j in jobs)),
+                                   _arr(VP, (j[2] for j in jobs)), s)
         return out
 
     def backward(self, P: dict, ctx: FwdCtx, gy: torch.Tensor, G: dict) -> None:
@@ -473,332 +545,311 @@ class EPDEngine:
         gradients of the shared 128x128 blocks are deferred: every step's row
         segments (G, X pairs, kept resident in HBM) are reduced at the end in
         one segmented MFMA pass per weight (pdg_wgrad_segments)."""
-        s = stream_handle(self.device)
-        plan = ctx.plan
-        N, E = plan.n_nodes, plan.n_edges
-        np_ = ctypes.byref(self._nparts)
+        b = self._bwd_begin(P, ctx, G)
+        self._bwd_decoder(P, ctx, b, gy)
+        for t in reversed(range(ctx.steps)):
+            self._bwd_step(P, ctx, b, t)
+        self._bwd_encoders(P, ctx, b)
+        self._bwd_wgrads(b)
+        self._bwd_epilogue(b)
+
+    def _bwd_begin(self, P, ctx: FwdCtx, G) -> _Bwd:
+        """W^T copies, the fused edge backward's slabs, the LayerNorm accumulators and pair rows."""
+        E, S = ctx.plan.n_edges, ctx.steps
         T = self.transposed(P)
-        st = ctx.stats
-        segs: dict[str, list] = {k: [] for k in ("W2", "Wc", "Wa", "Wb", "Wn2", "Wn1a", "Wn1b", "d1", "ne2", "ee2")}
         fused = self.fused_edge_wgrad
-        # LayerNorm backward scalars without finalize launches: every column-sum producer adds its
-        # per-block rows into the group accumulator and writes per-block (S1, S2) pairs; the consumer
-        # kernel reduces the pairs (include/pdivgnn.h, pdg_ln_colsum)
+        b = _Bwd(s=stream_handle(self.device), G=G, T=T, S=S, fused=fused, e_sum=fused and self.gz1e_from_gc,
+                 accs=None, pairs=None)
         if fused:
             # the three fused weight-gradient slab sets (W2, Wc, the edge encoder's W2) are written by the
             # first call of the backward (slab_init) and need no fill; the LayerNorm column-sum
             # accumulators are zeroed (one fill launch)
-            nse = self._nslabs_e
             # (an edgeless batch runs no edge kernel: zeros, so the edge weights get zero gradients)
-            sl = (torch.empty if E else torch.zeros)(3, nse, L * L + L, dtype=torch.float32, device=self.device)
-            slabs_w2, slabs_wc, slabs_ee = sl[0], sl[1], sl[2]
+            sl = (torch.empty if E else torch.zeros)(3, self._nslabs_e, L * L + L, dtype=torch.float32,
+                                                     device=self.device)
+            b.slabs_w2, b.slabs_wc, b.slabs_ee = sl[0], sl[1], sl[2]
             acc = torch.zeros(self._ln_acc.shape, dtype=torch.float64, device=self.device)
         else:
             acc = self._ln_acc
             acc.zero_()
-        reds = []   # deferred slab reductions (in the one pdg_bwd_epilogue launch at the end)
-        epi_narrow = []   # narrow weight-gradient finalizes for pdg_bwd_epilogue
-        epi_enc = None    # the edge encoder's first-layer sums for pdg_bwd_epilogue
-        ACC_N, ACC_E, ACC_NE, ACC_EE = (acc[i] for i in range(4))
-        S = ctx.steps
-        pairs = torch.empty(3 * S + 2, self.max_blocks * 2, dtype=torch.float64, device=self.device)
-        PN, PM, PE = (lambda t: pairs[t]), (lambda t: pairs[S + t]), (lambda t: pairs[2 * S + t])
-        P_NENC, P_EENC = pairs[3 * S], pairs[3 * S + 1]
-        g_node, g_edge = P["processor.node_net.4.weight"], P["processor.edge_net.4.weight"]
-        sync_slot = [0]
+        b.accs = tuple(acc[i] for i in range(4))
+        b.pairs = torch.empty(3 * S + 2, self.max_blocks * 2, dtype=torch.float64, device=self.device)
+        return b
 
-        def src(pp, n):
-            """(pairs pointer, count) for a consumer; sync DP mode reduces them first and
-            all-reduces the (S1, S2) pair over the ranks (global-minibatch LayerNorm)."""
-            if self.sync is None:
-                return _p(pp), n
-            out = self._sync_pairs[sync_slot[0] % 8]
-            sync_slot[0] += 1
-            lib.pdg_ln_partials_sum(_p(pp), n, _p(out), s)
-            self._t("sync_collective", lambda: torch.distributed.all_reduce(out, group=self.sync[0]))
-            return _p(out), 1
+    def _pairs_src(self, b: _Bwd, pp, n: int):
+        """(pairs pointer, count) for a consumer; sync DP mode reduces them first and
+        all-reduces the (S1, S2) pair over the ranks (global-minibatch LayerNorm)."""
+        if self.sync is None:
+            return _p(pp), n
+        out = self._sync_pairs[b.sync_slot % 8]
+        b.sync_slot += 1
+        lib.pdg_ln_partials_sum(_p(pp), n, _p(out), b.s)
+        self._t("sync_collective", lambda: torch.distributed.all_reduce(out, group=self.sync[0]))
+        return _p(out), 1
 
-        def edge_ln_pairs(pp, gy_rows, a2, st_ptr, accb, g):
-            """Pairs of the LayerNorm that produced an edge state e: fused mode has them from
-            pdg_edge_gout_wc (written while producing gy_rows = d loss / d e)."""
-            if not fused:
-                lib.pdg_ln_colsum(E, _p(gy_rows), None, _p(a2), st_ptr, _p(accb), np_, _p(g), _p(pp), 1, s)
-                return pp, self._nparts.value
-            return pp, nse
+    def _ln_producing(self, P, ctx: FwdCtx, b: _Bwd, kind: str, t: int):
+        """The LayerNorm whose output, plus the residual, is x_t (kind "n") or e_t (kind "e"): step t-1's
+        node_net / edge_net LayerNorm, or at t == 0 the encoder's.  Returns (its column-sum accumulator,
+        its row of pairs, its input a2, pointer to its statistics, its weight)."""
+        st = ctx.stats
+        if t > 0:
+            d = ctx.per_step[t - 1]
+            if kind == "n":
+                return b.accs[0], b.PN(t - 1), d["a2n"], st[d["i_n"]], P["processor.node_net.4.weight"]
+            return b.accs[1], b.PE(t - 1), d["a2e"], st[d["i_e"]], P["processor.edge_net.4.weight"]
+        if kind == "n":
+            return b.accs[2], b.pairs[3 * b.S], ctx.a2_ne, st[0], P["node_encoder.4.weight"]
+        return b.accs[3], b.pairs[3 * b.S + 1], ctx.a2_ee, st[1], P["edge_encoder.4.weight"]
 
+    def _edge_ln_pairs(self, ctx: FwdCtx, b: _Bwd, pp, gy_rows, a2, st_ptr, acc, g):
+        """(pairs pointer, count), for its consumer, of a LayerNorm that produced an edge state e with
+        gy_rows = d loss / d e: the fused backward has the pairs from the pdg_edge_gout_wc that wrote
+        gy_rows (one block per CU), the unfused one runs pdg_ln_colsum."""
+        if b.fused:
+            return self._pairs_src(b, pp, self._nslabs_e)
+        lib.pdg_ln_colsum(ctx.plan.n_edges, _p(gy_rows), None, _p(a2), st_ptr, _p(acc),
+                          ctypes.byref(self._nparts), _p(g), _p(pp), 1, b.s)
+        return self._pairs_src(b, pp, self._nparts.value)
+
+    def _bwd_decoder(self, P, ctx: FwdCtx, b: _Bwd, gy) -> None:
+        """The decoder's backward, and the buffers of the input-gradient chain."""
+        N, E, S, nse = ctx.plan.n_nodes, ctx.plan.n_edges, b.S, self._nslabs_e
         gy = gy.contiguous()
         if ctx.scale_output:
             gy = gy * P["_std_local_stress"]
-        # decoder
         gz1d, gx = self._empty(N, L), self._empty(N, L)
         dl = ctx.per_step[S - 1]
-        if self.nbwd_coop:   # + the column sums of the last node LayerNorm (upstream gradient: gx)
-            # + node_decoder.2's weight / bias gradient from the same a1d / gy rows (block partials)
-            self._t("decoder_bwd", lib.pdg_decoder_bwd_coop, N, _p(gy), _p(ctx.a1d), _p(P["node_decoder.2.weight"]),
-                    _p(T["Wd1T"]), _p(gz1d), _p(gx), _p(dl["a2n"]), st[dl["i_n"]], _p(ACC_N), _p(g_node),
-                    _p(PN(S - 1)), 1, _p(self._part_narrow_d), self._nslabs_e, s)
-            self._nparts.value = self._nslabs_e
-            epi_narrow.append((self._part_narrow_d, self._nslabs_e, 3, 1, G["node_decoder.2.weight"], None,
-                               G["node_decoder.2.bias"]))
-        else:
-            lib.pdg_decoder_bwd(N, _p(gy), _p(ctx.a1d), _p(P["node_decoder.2.weight"]), _p(T["Wd1T"]), _p(gz1d),
-                                _p(gx), s)
-            lib.pdg_wgrad_narrow(N, _p(ctx.a1d), _p(gy), 3, 1, _p(self._part_narrow), _p(G["node_decoder.2.weight"]),
-                                 None, _p(G["node_decoder.2.bias"]), s)
-        segs["d1"].append((gz1d, ctx.x_S, N))
+        # + the column sums of the last node LayerNorm (upstream gradient: gx; for the earlier steps the next
+        # step's pdg_gemm_sum2_coop produces them), + node_decoder.2's weight / bias gradient from the same
+        # a1d / gy rows (block partials)
+        self._t("decoder_bwd", lib.pdg_decoder_bwd_coop, N, _p(gy), _p(ctx.a1d), _p(P["node_decoder.2.weight"]),
+                _p(b.T["Wd1T"]), _p(gz1d), _p(gx), _p(dl["a2n"]), ctx.stats[dl["i_n"]], _p(b.accs[0]),
+                _p(P["processor.node_net.4.weight"]), _p(b.PN(S - 1)), 1, _p(self._part_narrow_d), nse, b.s)
+        b.epi_narrow.append((self._part_narrow_d, nse, 3, 1, b.G["node_decoder.2.weight"], None,
+                             b.G["node_decoder.2.bias"]))
+        b.segs["d1"].append((gz1d, ctx.x_S, N))
+        b.gaggr, b.gx_part, b.gx_t = (self._empty(N, L) for _ in range(3))
+        b.gz1m = self._empty(E, L)
+        b.gz1e = None if b.e_sum else self._empty(E, L)
+        b.ge_bufs = [self._empty(E, L), self._empty(E, L)]
+        b.gC_fused = self._empty(E, L) if b.fused else None
+        b.gx_next, b.n_node = gx, nse
 
-        ge_next = None              # d loss / d e_S: the last edge update has no consumer
-        gaggr, gx_part, gx_t = (self._empty(N, L) for _ in range(3))
-        e_sum = fused and self.gz1e_from_gc   # gz1e never stored: pdg_pq_scatter_bwd takes gC - gz1m
-        gz1m = self._empty(E, L)
-        gz1e = None if e_sum else self._empty(E, L)
-        ge_bufs = [self._empty(E, L), self._empty(E, L)]
-        gC_fused = self._empty(E, L) if fused else None
-        gx_next = gx
-        # node LayerNorm of the last step (upstream gradient: the decoder's); for the earlier steps
-        # the previous iteration's pdg_gemm_sum2_rw produces these partials
-        if not self.nbwd_coop:
-            lib.pdg_ln_colsum(N, _p(gx_next), None, _p(dl["a2n"]), st[dl["i_n"]], _p(ACC_N), np_, _p(g_node),
-                              _p(PN(S - 1)), 1, s)
-        n_node = self._nparts.value
-        n_edge = 0
-        for t in reversed(range(S)):
-            d = ctx.per_step[t]
-            eu = d["eu"]
-            assert E == 0 or eu == (ge_next is not None)
-            gz2n, gz1n, gP, gQ = (self._empty(N, L) for _ in range(4))
-            gC = gC_fused if fused else self._empty(E, L)   # fused: consumed within the step
-            if fused and not eu:
-                gC = gz1m   # message branch only: gC = gz1m, written once (pdg_edge_bwd_w2)
-            gz2m = None if fused else self._empty(E, L)
-            gz2e = self._empty(E, L) if (eu and not fused) else None
-            ge_out = ge_bufs[t % 2]
-            # node_net backward (n_t = LN_n(a2n_t), gy = gx_next; x_{t+1} = n_t + x_t)
-            pn, nn = src(PN(t), n_node)
-            if self.nbwd_coop:
-                self._t("node_bwd", lib.pdg_node_bwd_coop, N, _p(gx_next), _p(d["a2n"]), _p(d["a1n"]),
-                        st[d["i_n"]], None, _p(g_node), _p(T["Wn2T"]), _p(T["Wn1aT"]), _p(T["Wn1bT"]), _p(gz2n),
-                        _p(gz1n), _p(gaggr), _p(gx_part), pn, nn, self._nslabs_e, s)
-            else:
-                self._t("node_bwd", lib.pdg_node_bwd, N, _p(gx_next), _p(d["a2n"]), _p(d["a1n"]), st[d["i_n"]],
-                        None, _p(g_node), _p(T["Wn2T"]), _p(T["Wn1aT"]), _p(T["Wn1bT"]), _p(gz2n), _p(gz1n),
-                        _p(gaggr), _p(gx_part), pn, nn, s)
-            if E == 0:             # no edge: P and Q feed nothing (models.py:215-222 on empty tensors)
-                gP.zero_()
-                gQ.zero_()
-            else:
-                # message LayerNorm: gy = gaggr[dst], summed per node with the forward's sum of xhat
-                lib.pdg_ln_colsum_nodes(N, _p(gaggr), _p(plan.rowptr_dst), _p(d["xs"]), _p(ACC_E), np_, _p(g_edge),
-                                        _p(PM(t)), 1, s)
-                pm, nm = src(PM(t), self._nparts.value)
-                pe, ne = None, 0
-                if eu:   # edge-update LayerNorm: gy = ge_next (per edge)
-                    pp, n_e = edge_ln_pairs(PE(t), ge_next, d["a2e"], st[d["i_e"]], ACC_E, g_edge)
-                    pe, ne = src(pp, n_e if not fused else n_edge)
-                if fused:
-                    self._t("edge_bwd" if eu else "edge_bwd_last", lib.pdg_edge_bwd_w2, E, _p(plan.dst), _p(gaggr),
-                            _p(ge_next), _p(d["a2m"]), _p(d["a1m"]), _p(d["a2e"]), _p(d["a1e"]), st[d["i_m"]],
-                            st[d["i_e"]] if eu else None, None, None, _p(g_edge), _p(T["W2T"]), _p(gz1m),
-                            _p(gz1e if eu else None), _p(gC), _p(slabs_w2), nse, pm, nm, pe, ne, int(t == S - 1), s)
-                    # the edge-update rows of the P/Q gather backward: gz1e, or gC (= gz1m + gz1e) with e_is_sum
-                    ge_rows, e_is_sum = (gC, 1) if (e_sum and eu) else (gz1e if eu else None, 0)
-                    # + the column sums / pairs of the LayerNorm that produced e_t (LN_e of step t-1, or the
-                    # edge encoder's)
-                    if t > 0:
-                        a2ln, st_ln, accb, gl, pp = (ctx.per_step[t - 1]["a2e"], st[ctx.per_step[t - 1]["i_e"]], ACC_E,
-                                                     g_edge, PE(t - 1))
-                    else:
-                        a2ln, st_ln, accb, gl, pp = ctx.a2_ee, st[1], ACC_EE, P["edge_encoder.4.weight"], P_EENC
-                    tail = (_p(d["e"]), _p(ge_next), _p(T["WcT"]), _p(ge_out), _p(slabs_wc), nse, _p(a2ln), st_ln,
-                            _p(accb), _p(gl), _p(pp), 1, int(t == S - 1), s)
-                    gout_fn, gout_args = lib.pdg_edge_gout_wc, (E, _p(gC)) + tail
-                    if not self.pq_first:
-                        self._t("edge_gout", gout_fn, *gout_args)
-                    n_edge = nse
-                else:
-                    self._t("edge_bwd" if eu else "edge_bwd_last", lib.pdg_edge_bwd, E, _p(plan.dst), _p(gaggr),
-                            _p(ge_next), _p(d["a2m"]), _p(d["a1m"]), _p(d["a2e"]), _p(d["a1e"]), st[d["i_m"]],
-                            st[d["i_e"]] if eu else None, None, None, _p(g_edge), _p(T["W2T"]), _p(T["WcT"]),
-                            _p(gz2m), _p(gz1m), _p(gz2e), _p(gz1e if eu else None), _p(gC), _p(ge_out), pm, nm, pe, ne, s)
-                    ge_rows, e_is_sum = gz1e if eu else None, 0
-                self._t("pq_scatter_bwd", lib.pdg_pq_scatter_bwd, N, _p(plan.rowptr_dst), _p(plan.rowptr_src),
-                        _p(plan.perm_src), _p(gz1m), _p(ge_rows), e_is_sum, _p(gP), _p(gQ), s)
-                if fused and self.pq_first:   # gz1m / gz1e read while still in the Infinity Cache
-                    self._t("edge_gout", gout_fn, *gout_args)
-            # gx_t, with the column sums / pairs of the LayerNorm whose output it is the gradient of:
-            # the node LayerNorm of step t-1, or the node encoder's
-            if t > 0:
-                a2n_prev, st_prev, accb, gl, pp = (ctx.per_step[t - 1]["a2n"], st[ctx.per_step[t - 1]["i_n"]], ACC_N,
-                                                   g_node, PN(t - 1))
-            else:
-                a2n_prev, st_prev, accb, gl, pp = ctx.a2_ne, st[0], ACC_NE, P["node_encoder.4.weight"], P_NENC
-            if self.gsum2_coop:
-                self._t("gemm_sum2", lib.pdg_gemm_sum2_coop, N, _p(gP), _p(gQ), _p(T["WaT"]), _p(T["WbT"]),
-                        _p(gx_part), _p(gx_t), _p(a2n_prev), st_prev, _p(accb), _p(gl), _p(pp), 1, self._nslabs_e, s)
-                self._nparts.value = self._nslabs_e
-            else:
-                self._t("gemm_sum2", lib.pdg_gemm_sum2_rw, N, _p(gP), _p(gQ), _p(T["WaT"]), _p(T["WbT"]),
-                        _p(gx_part), _p(gx_t), _p(a2n_prev), st_prev, _p(accb), np_, _p(gl), _p(pp), 1, s)
-            n_node = self._nparts.value
-            if not fused and E:
-                segs["W2"].append((gz2m, d["a1m"], E))
-                if eu:
-                    segs["W2"].append((gz2e, d["a1e"], E))
-                segs["Wc"].append((gC, d["e"], E))
-            segs["Wa"].append((gP, d["x"], N))
-            segs["Wb"].append((gQ, d["x"], N))
-            segs["Wn2"].append((gz2n, d["a1n"], N))
-            segs["Wn1a"].append((gz1n, d["aggr"], N))
-            segs["Wn1b"].append((gz1n, d["x"], N))
-            if self.probe is not None:
-                self.probe[t] = dict(gx=gx_t.clone(), ge=ge_out.clone() if E else None, gaggr=gaggr.clone())
-            gx_next, gx_t = gx_t, gx_next
-            ge_next = ge_out
-        # encoders
+    def _bwd_step(self, P, ctx: FwdCtx, b: _Bwd, t: int) -> None:
+        """Step t's input gradients: node_net backward, edge backward + P/Q gather backward, then
+        gx_t (pdg_gemm_sum2_coop); its weight-gradient segments are queued."""
+        N, E, T, s, nse = ctx.plan.n_nodes, ctx.plan.n_edges, b.T, b.s, self._nslabs_e
+        d = ctx.per_step[t]
+        eu, fused = d["eu"], b.fused
+        assert E == 0 or eu == (b.ge_next is not None)
+        gz2n, gz1n, gP, gQ = (self._empty(N, L) for _ in range(4))
+        gC = b.gC_fused if fused else self._empty(E, L)   # fused: consumed within the step
+        if fused and not eu:
+            gC = b.gz1m   # message branch only: gC = gz1m, written once (pdg_edge_bwd_w2)
+        gz2m = None if fused else self._empty(E, L)
+        gz2e = self._empty(E, L) if (eu and not fused) else None
+        ge_out = b.ge_bufs[t % 2]
+        # node_net backward (n_t = LN_n(a2n_t), gy = gx_next; x_{t+1} = n_t + x_t), three W^T products in bf16x6
+        pn, nn = self._pairs_src(b, b.PN(t), b.n_node)
+        self._t("node_bwd", lib.pdg_node_bwd_coop, N, _p(b.gx_next), _p(d["a2n"]), _p(d["a1n"]),
+                ctx.stats[d["i_n"]], None, _p(P["processor.node_net.4.weight"]), _p(T["Wn2T"]), _p(T["Wn1aT"]),
+                _p(T["Wn1bT"]), _p(gz2n), _p(gz1n), _p(b.gaggr), _p(b.gx_part), pn, nn, nse, s)
+        if E == 0:             # no edge: P and Q feed nothing (models.py:215-222 on empty tensors)
+            gP.zero_()
+            gQ.zero_()
+        else:
+            self._bwd_edge_net(P, ctx, b, t, gC, gz2m, gz2e, ge_out, gP, gQ)
+        # gx_t in bf16x6, with the column sums / pairs of the LayerNorm whose output it is the gradient of
+        acc, pp, a2n_prev, st_prev, gl = self._ln_producing(P, ctx, b, "n", t)
+        self._t("gemm_sum2", lib.pdg_gemm_sum2_coop, N, _p(gP), _p(gQ), _p(T["WaT"]), _p(T["WbT"]),
+                _p(b.gx_part), _p(b.gx_t), _p(a2n_prev), st_prev, _p(acc), _p(gl), _p(pp), 1, nse, s)
+        b.n_node = nse
+        segs = b.segs
+        if not fused and E:
+            segs["W2"].append((gz2m, d["a1m"], E))
+            if eu:
+                segs["W2"].append((gz2e, d["a1e"], E))
+            segs["Wc"].append((gC, d["e"], E))
+        segs["Wa"].append((gP, d["x"], N))
+        segs["Wb"].append((gQ, d["x"], N))
+        segs["Wn2"].append((gz2n, d["a1n"], N))
+        segs["Wn1a"].append((gz1n, d["aggr"], N))
+        segs["Wn1b"].append((gz1n, d["x"], N))
+        if self.probe is not None:
+            self.probe[t] = dict(gx=b.gx_t.clone(), ge=ge_out.clone() if E else None, gaggr=b.gaggr.clone())
+        b.gx_next, b.gx_t = b.gx_t, b.gx_next
+        b.ge_next = ge_out
+
+    def _bwd_edge_net(self, P, ctx: FwdCtx, b: _Bwd, t: int, gC, gz2m, gz2e, ge_out, gP, gQ) -> None:
+        """Both edge_net evaluations of step t backwards (E > 0): ge_out = d loss / d e_t, and gP / gQ
+        through the P/Q gather; fused, also the W2 / Wc weight gradients (slabs)."""
+        plan, T, s, nse = ctx.plan, b.T, b.s, self._nslabs_e
+        N, E, st = plan.n_nodes, plan.n_edges, ctx.stats
+        d = ctx.per_step[t]
+        eu, last = d["eu"], int(t == b.S - 1)
+        g_edge = P["processor.edge_net.4.weight"]
+        # message LayerNorm: gy = gaggr[dst], summed per node with the forward's sum of xhat
+        lib.pdg_ln_colsum_nodes(N, _p(b.gaggr), _p(plan.rowptr_dst), _p(d["xs"]), _p(b.accs[1]),
+                                ctypes.byref(self._nparts), _p(g_edge), _p(b.PM(t)), 1, s)
+        pm, nm = self._pairs_src(b, b.PM(t), self._nparts.value)
+        pe, ne = None, 0
+        if eu:   # edge-update LayerNorm: gy = ge_next (per edge)
+            pe, ne = self._edge_ln_pairs(ctx, b, b.PE(t), b.ge_next, d["a2e"], st[d["i_e"]], b.accs[1], g_edge)
+        if b.fused:
+            self._t("edge_bwd" if eu else "edge_bwd_last", lib.pdg_edge_bwd_w2, E, _p(plan.dst), _p(b.gaggr),
+                    _p(b.ge_next), _p(d["a2m"]), _p(d["a1m"]), _p(d["a2e"]), _p(d["a1e"]), st[d["i_m"]],
+                    st[d["i_e"]] if eu else None, None, None, _p(g_edge), _p(T["W2T"]), _p(b.gz1m),
+                    _p(b.gz1e if eu else None), _p(gC), _p(b.slabs_w2), nse, pm, nm, pe, ne, last, s)
+            # the edge-update rows of the P/Q gather backward: gz1e, or gC (= gz1m + gz1e) with e_is_sum
+            ge_rows, e_is_sum = (gC, 1) if (b.e_sum and eu) else (b.gz1e if eu else None, 0)
+        else:
+            self._t("edge_bwd" if eu else "edge_bwd_last", lib.pdg_edge_bwd, E, _p(plan.dst), _p(b.gaggr),
+                    _p(b.ge_next), _p(d["a2m"]), _p(d["a1m"]), _p(d["a2e"]), _p(d["a1e"]), st[d["i_m"]],
+                    st[d["i_e"]] if eu else None, None, None, _p(g_edge), _p(T["W2T"]), _p(T["WcT"]),
+                    _p(gz2m), _p(b.gz1m), _p(gz2e), _p(b.gz1e if eu else None), _p(gC), _p(ge_out), pm, nm, pe,
+                    ne, s)
+            ge_rows, e_is_sum = b.gz1e if eu else None, 0
+        # the P/Q gather backward before the Wc pass: gz1m / gz1e are re-read while still in the Infinity Cache
+        self._t("pq_scatter_bwd", lib.pdg_pq_scatter_bwd, N, _p(plan.rowptr_dst), _p(plan.rowptr_src),
+                _p(plan.perm_src), _p(b.gz1m), _p(ge_rows), e_is_sum, _p(gP), _p(gQ), s)
+        if b.fused:
+            # ge_out and the Wc weight gradient, + the column sums / pairs of the LayerNorm that produced e_t
+            acc, pp, a2ln, st_ln, gl = self._ln_producing(P, ctx, b, "e", t)
+            self._t("edge_gout", lib.pdg_edge_gout_wc, E, _p(gC), _p(d["e"]), _p(b.ge_next), _p(T["WcT"]),
+                    _p(ge_out), _p(b.slabs_wc), nse, _p(a2ln), st_ln, _p(acc), _p(gl), _p(pp), 1, last, s)
+
+    def _bwd_encoders(self, P, ctx: FwdCtx, b: _Bwd) -> None:
+        """The two encoders' backward; their narrow first-layer gradients go to the epilogue (fused) or
+        pdg_wgrad_narrow."""
+        N, E, T, G, s, nse = ctx.plan.n_nodes, ctx.plan.n_edges, b.T, b.G, b.s, self._nslabs_e
         gz2 = self._empty(N, L)
-        gz1 = None if self.nbwd_coop else self._empty(N, L)
-        pn, nn = src(P_NENC, n_node)
-        if self.nbwd_coop:   # the node encoder's backward, bf16x6 (pdg_mlp2_bwd_coop), + its first layer's
-            # weight / bias gradient from gz1 and the encoder input (block partials; gz1 is not stored)
-            self._t("node_enc_bwd", lib.pdg_mlp2_bwd_coop, N, _p(gx_next), _p(ctx.a2_ne), _p(ctx.a1_ne), st[0], None,
-                    _p(P["node_encoder.4.weight"]), _p(T["Wne2T"]), _p(gz2), None, pn, nn, _p(ctx.x_in),
-                    _p(self._part_narrow_ne), self._nslabs_e, s)
-            epi_narrow.append((self._part_narrow_ne, self._nslabs_e, 6, 0, G["node_encoder.0.weight"],
-                               G["node_encoder.0.bias"], None))
+        _, pp, a2, st_ln, gl = self._ln_producing(P, ctx, b, "n", 0)
+        pn, nn = self._pairs_src(b, pp, b.n_node)
+        # bf16x6 (pdg_mlp2_bwd_coop), + the first layer's weight / bias gradient from gz1 and the encoder
+        # input (block partials; gz1 is not stored)
+        self._t("node_enc_bwd", lib.pdg_mlp2_bwd_coop, N, _p(b.gx_next), _p(a2), _p(ctx.a1_ne), st_ln, None,
+                _p(gl), _p(T["Wne2T"]), _p(gz2), None, pn, nn, _p(ctx.x_in), _p(self._part_narrow_ne), nse, s)
+        b.epi_narrow.append((self._part_narrow_ne, nse, 6, 0, G["node_encoder.0.weight"],
+                             G["node_encoder.0.bias"], None))
+        b.segs["ne2"].append((gz2, ctx.a1_ne, N))
+        if not E:
+            return
+        acc, pp, a2, st_ln, gl = self._ln_producing(P, ctx, b, "e", 0)
+        pe, ne = self._edge_ln_pairs(ctx, b, pp, b.ge_next, a2, st_ln, acc, gl)
+        if b.fused:   # one pass: weight gradients in slabs, the 1 -> 128 layer's as per-block sums
+            nsum = torch.empty(nse, 2 * L, dtype=torch.float64, device=self.device)
+            self._t("edge_enc_bwd", lib.pdg_edge_enc_bwd, E, _p(b.ge_next), _p(a2), _p(ctx.e_in),
+                    _p(P["edge_encoder.0.weight"]), _p(P["edge_encoder.0.bias"]), st_ln, None, pe, ne,
+                    _p(gl), _p(T["Wee2T"]), _p(b.slabs_ee), _p(nsum), nse, 1, s)
+            b.reds.append((b.slabs_ee, nse, G["edge_encoder.2.weight"], L, 0, G["edge_encoder.2.bias"]))
+            b.epi_enc = (nsum, nse, G["edge_encoder.0.weight"], G["edge_encoder.0.bias"])
         else:
-            lib.pdg_mlp2_bwd(N, _p(gx_next), None, _p(ctx.a2_ne), _p(ctx.a1_ne), st[0], None,
-                             _p(P["node_encoder.4.weight"]), _p(T["Wne2T"]), _p(gz2), _p(gz1), pn, nn, s)
-            lib.pdg_wgrad_narrow(N, _p(gz1), _p(ctx.x_in), 6, 0, _p(self._part_narrow),
-                                 _p(G["node_encoder.0.weight"]), _p(G["node_encoder.0.bias"]), None, s)
-        segs["ne2"].append((gz2, ctx.a1_ne, N))
-        if E:
-            pp, n_e = edge_ln_pairs(P_EENC, ge_next, ctx.a2_ee, st[1], ACC_EE, P["edge_encoder.4.weight"])
-            pe, ne = src(pp, n_e if not fused else n_edge)
-            if fused:   # one pass: weight gradients in slabs (zeroed above), the 1 -> 128 layer's as per-block sums
-                nsum = torch.empty(nse, 2 * L, dtype=torch.float64, device=self.device)
-                self._t("edge_enc_bwd", lib.pdg_edge_enc_bwd, E, _p(ge_next), _p(ctx.a2_ee), _p(ctx.e_in),
-                        _p(P["edge_encoder.0.weight"]), _p(P["edge_encoder.0.bias"]), st[1], None, pe, ne,
-                        _p(P["edge_encoder.4.weight"]), _p(T["Wee2T"]), _p(slabs_ee), _p(nsum), nse, 1, s)
-                reds.append((slabs_ee, nse, G["edge_encoder.2.weight"], L, 0, G["edge_encoder.2.bias"]))
-                epi_enc = (nsum, nse, G["edge_encoder.0.weight"], G["edge_encoder.0.bias"])
-            else:
-                gz2e_, gz1e_ = self._empty(E, L), self._empty(E, L)
-                lib.pdg_mlp2_bwd(E, _p(ge_next), None, _p(ctx.a2_ee), _p(ctx.a1_ee), st[1], None,
-                                 _p(P["edge_encoder.4.weight"]), _p(T["Wee2T"]), _p(gz2e_), _p(gz1e_), pe, ne, s)
-                segs["ee2"].append((gz2e_, ctx.a1_ee, E))
-                lib.pdg_wgrad_narrow(E, _p(gz1e_), _p(ctx.e_in), 1, 0, _p(self._part_narrow),
-                                     _p(G["edge_encoder.0.weight"]), _p(G["edge_encoder.0.bias"]), None, s)
-        # deferred weight gradients: one segmented pass + slab reduction per shared weight block
-        red = [
-            ("W2", "processor.edge_net.2.weight", L, 0, "processor.edge_net.2.bias"),
-            ("Wc", "processor.edge_net.0.weight", 3 * L, 2 * L, "processor.edge_net.0.bias"),
-            ("Wa", "processor.edge_net.0.weight", 3 * L, 0, None),
-            ("Wb", "processor.edge_net.0.weight", 3 * L, L, None),
-            ("Wn2", "processor.node_net.2.weight", L, 0, "processor.node_net.2.bias"),
-            ("Wn1a", "processor.node_net.0.weight", 2 * L, 0, "processor.node_net.0.bias"),
-            ("Wn1b", "processor.node_net.0.weight", 2 * L, L, None),
-            ("d1", "node_decoder.0.weight", L, 0, "node_decoder.0.bias"),
-            ("ne2", "node_encoder.2.weight", L, 0, "node_encoder.2.bias"),
-            ("ee2", "edge_encoder.2.weight", L, 0, "edge_encoder.2.bias"),
-        ]
-        ns = self._nslabs
-        slab_sets = self.__dict__.setdefault("_slab_sets", {})
+            gz2e, gz1e = self._empty(E, L), self._empty(E, L)
+            lib.pdg_mlp2_bwd(E, _p(b.ge_next), None, _p(a2), _p(ctx.a1_ee), st_ln, None, _p(gl), _p(T["Wee2T"]),
+                             _p(gz2e), _p(gz1e), pe, ne, s)
+            b.segs["ee2"].append((gz2e, ctx.a1_ee, E))
+            lib.pdg_wgrad_narrow(E, _p(gz1e), _p(ctx.e_in), 1, 0, _p(self._part_narrow),
+                                 _p(G["edge_encoder.0.weight"]), _p(G["edge_encoder.0.bias"]), None, s)
 
-        def slab_set(key):
-            """The slab set of one deferred weight (the reductions run batched at the end), allocated
-            the first time that weight has a segment pass: with the fused edge backward and the pair
-            passes only node_net.2, the decoder and the node encoder need one."""
-            if key not in slab_sets:
-                slab_sets[key] = torch.empty(ns, L * L + L, dtype=torch.float32, device=self.device)
-            return slab_sets[key]
-        # the weight pairs that share an operand, one pass each (pdg_wgrad_pairs): Wa / Wb against x
-        # (gP, gQ), node_net.0's halves from gz1n (against aggr, x)
-        nsp = self._nslabs_p
-        if getattr(self, "_slabs_p", None) is None or self._slabs_p.device != self.device:
+    def _reduce(self, b: _Bwd, slabs, n: int, wname: str, ld: int, col0: int, bname, later: bool) -> None:
+        """Add a slab set into G[wname][:, col0:col0+128] (and G[bname]): in the epilogue, or at once where
+        the next chunk overwrites the slabs."""
+        job = (slabs, n, b.G[wname], ld, col0, b.G[bname] if bname else None)
+        if later:
+            b.reds.append(job)
+        else:
+            lib.pdg_wgrad_reduce(_p(slabs), n, _p(job[2]), ld, col0, _p(job[5]), b.s)
+
+    def _bwd_wgrads(self, b: _Bwd) -> None:
+        """The deferred weight gradients: one segmented pass + slab reduction per shared weight block."""
+        self._wgrad_pairs(b)
+        self._wgrad_segments(b)
+        if b.fused:   # the slabs of the fused edge backward, accumulated over all steps
+            self._reduce(b, b.slabs_w2, self._nslabs_e, "processor.edge_net.2.weight", L, 0,
+                         "processor.edge_net.2.bias", True)
+            self._reduce(b, b.slabs_wc, self._nslabs_e, "processor.edge_net.0.weight", 3 * L, 2 * L,
+                         "processor.edge_net.0.bias", True)
+
+    def _wgrad_pairs(self, b: _Bwd) -> None:
+        """The weight pairs that share an operand, one pass each (pdg_wgrad_pairs): Wa / Wb against x
+        (gP, gQ), node_net.0's halves from gz1n (against aggr, x); at most 32 segments per launch."""
+        segs, nsp = b.segs, self._nslabs_p
+        if self._slabs_p is None:
             self._slabs_p = torch.empty(2, 2, nsp, L * L + L, dtype=torch.float32, device=self.device)
-        pairs_w = [
-            (1, [(g, q, x, n) for (g, x, n), (q, _, _) in zip(segs.pop("Wa"), segs.pop("Wb"))],
+        pair_sets = [
+            (1, [(g, q, x, n) for (g, x, n), (q, _, _) in zip(segs["Wa"], segs["Wb"])],
              ("processor.edge_net.0.weight", 3 * L, 0, None), ("processor.edge_net.0.weight", 3 * L, L, None)),
-            (0, [(g, a, x, n) for (g, a, n), (_, x, _) in zip(segs.pop("Wn1a"), segs.pop("Wn1b"))],
+            (0, [(g, a, x, n) for (g, a, n), (_, x, _) in zip(segs["Wn1a"], segs["Wn1b"])],
              ("processor.node_net.0.weight", 2 * L, 0, "processor.node_net.0.bias"),
              ("processor.node_net.0.weight", 2 * L, L, None)),
         ]
-        def reduce_now_or_later(slabs, n, wname, ld, col0, bname, later):
-            job = (slabs, n, G[wname], ld, col0, G[bname] if bname else None)
-            if later:
-                reds.append(job)
-            else:   # a slab set reused by the next chunk: reduce before it is overwritten
-                lib.pdg_wgrad_reduce(_p(slabs), n, _p(job[2]), ld, col0, _p(job[5]), s)
-
-        for gi, (shx, sl, (w0n, ld0, c00, b0n), (w1n, ld1, c01, b1n)) in enumerate(pairs_w):
+        for gi, (shx, sl, w0, w1) in enumerate(pair_sets):
             sp0, sp1 = self._slabs_p[gi]
+            later = len(sl) <= 32   # one chunk: nothing overwrites the slabs before the epilogue
             for c0 in range(0, len(sl), 32):
                 chunk = sl[c0:c0 + 32]
-                n = len(chunk)
-                arr = [(ctypes.c_void_p * n)(*[t[k].data_ptr() for t in chunk]) for k in range(3)]
-                rw = (ctypes.c_int * n)(*[t[3] for t in chunk])
-                self._t("wgrad_pair", lib.pdg_wgrad_pairs, n, arr[0], arr[1], arr[2], rw, shx, _p(sp0), _p(sp1), nsp,
-                        s)
-                later = len(sl) <= 32
-                reduce_now_or_later(sp0, nsp, w0n, ld0, c00, b0n, later)
-                reduce_now_or_later(sp1, nsp, w1n, ld1, c01, b1n, later)
-        red_k = [r for r in red if r[0] in segs]
-        # weights of at most 32 segments: up to three passes per launch (pdg_wgrad_segments_batch)
-        small = [r for r in red_k if 0 < len(segs[r[0]]) <= 32]
+                self._t("wgrad_pair", lib.pdg_wgrad_pairs, len(chunk), _arr(VP, (c[0].data_ptr() for c in chunk)),
+                        _arr(VP, (c[1].data_ptr() for c in chunk)), _arr(VP, (c[2].data_ptr() for c in chunk)),
+                        _arr(IA, (c[3] for c in chunk)), shx, _p(sp0), _p(sp1), nsp, b.s)
+                self._reduce(b, sp0, nsp, *w0, later)
+                self._reduce(b, sp1, nsp, *w1, later)
+
+    def _slab_set(self, key: str):
+        """The slab set of one deferred weight, allocated the first time that weight has a segment pass:
+        with the fused edge backward and the pair passes only node_net.2, the decoder and the node encoder
+        need one."""
+        if key not in self._slab_sets:
+            self._slab_sets[key] = torch.empty(self._nslabs, L * L + L, dtype=torch.float32, device=self.device)
+        return self._slab_sets[key]
+
+    def _wgrad_segments(self, b: _Bwd) -> None:
+        """The other deferred weights (pdg_wgrad_segments): those of at most 32 segments up to three per
+        launch, their reductions left to the epilogue; the larger ones in chunks of 32 segments, each
+        reduced at once (the next chunk overwrites the slab set)."""
+        segs, ns, s = b.segs, self._nslabs, b.s
+        small = [r for r in _DEFERRED if 0 < len(segs[r[0]]) <= 32]
         for c0 in range(0, len(small), 3):
             grp = small[c0:c0 + 3]
-            segl = [segs[r[0]] for r in grp]
-            flat = [t for sl in segl for t in sl]
-            n = len(flat)
+            flat = [seg for r in grp for seg in segs[r[0]]]
             self._t("wgrad_batch", lib.pdg_wgrad_segments_batch, len(grp),
-                    (ctypes.c_int * len(grp))(*[len(sl) for sl in segl]),
-                    (ctypes.c_void_p * n)(*[g.data_ptr() for g, _, _ in flat]),
-                    (ctypes.c_void_p * n)(*[x.data_ptr() for _, x, _ in flat]),
-                    (ctypes.c_int * n)(*[r for _, _, r in flat]),
-                    (ctypes.c_void_p * len(grp))(*[_p(slab_set(k[0])) for k in grp]),
-                    ns, s)
+                    _arr(IA, (len(segs[r[0]]) for r in grp)), _arr(VP, (g.data_ptr() for g, _, _ in flat)),
+                    _arr(VP, (x.data_ptr() for _, x, _ in flat)), _arr(IA, (n for _, _, n in flat)),
+                    _arr(VP, (_p(self._slab_set(r[0])) for r in grp)), ns, s)
             for key, wname, ld, col0, bname in grp:
-                reduce_now_or_later(slab_set(key), ns, wname, ld, col0, bname, True)
-        for key, wname, ld, col0, bname in red_k:
+                self._reduce(b, self._slab_set(key), ns, wname, ld, col0, bname, True)
+        for key, wname, ld, col0, bname in _DEFERRED:
             sl = segs[key]
             if len(sl) <= 32:
                 continue
-            slabs_k = slab_set(key)
+            slabs = self._slab_set(key)
             for c0 in range(0, len(sl), 32):
                 chunk = sl[c0:c0 + 32]
-                n = len(chunk)
-                gp = (ctypes.c_void_p * n)(*[g.data_ptr() for g, _, _ in chunk])
-                xp = (ctypes.c_void_p * n)(*[x.data_ptr() for _, x, _ in chunk])
-                rw = (ctypes.c_int * n)(*[r for _, _, r in chunk])
-                self._t("wgrad_" + key, lib.pdg_wgrad_segments, n, gp, xp, rw, _p(slabs_k), ns, s)
-                reduce_now_or_later(slabs_k, ns, wname, ld, col0, bname, len(sl) <= 32)
-        if fused:   # the slabs of the fused edge backward, accumulated over all steps
-            reds.append((slabs_w2, nse, G["processor.edge_net.2.weight"], L, 0, G["processor.edge_net.2.bias"]))
-            reds.append((slabs_wc, nse, G["processor.edge_net.0.weight"], 3 * L, 2 * L,
-                         G["processor.edge_net.0.bias"]))
-        # every end-of-backward reduction in one launch (pdg_bwd_epilogue): the deferred slab reductions,
-        # the LayerNorm weight / bias gradients of the four accumulator groups, the narrow weight gradients
-        # and the edge encoder's first layer (more than 16 slab sets: the rest in pdg_wgrad_reduce_batch)
-        VP, IA = ctypes.c_void_p, ctypes.c_int
+                self._t("wgrad_" + key, lib.pdg_wgrad_segments, len(chunk),
+                        _arr(VP, (g.data_ptr() for g, _, _ in chunk)), _arr(VP, (x.data_ptr() for _, x, _ in chunk)),
+                        _arr(IA, (n for _, _, n in chunk)), _p(slabs), ns, s)
+                self._reduce(b, slabs, ns, wname, ld, col0, bname, False)
+
+    def _bwd_epilogue(self, b: _Bwd) -> None:
+        """Every end-of-backward reduction in one launch (pdg_bwd_epilogue): the deferred slab reductions,
+        the LayerNorm weight / bias gradients of the four accumulator groups, the narrow weight gradients
+        and the edge encoder's first layer (more than 16 slab sets: the rest in pdg_wgrad_reduce_batch)."""
+        G, reds, narrow, enc = b.G, b.reds, b.epi_narrow, b.epi_enc
         for c0 in range(16, len(reds), 16):
             jb = reds[c0:c0 + 16]
-            n = len(jb)
-            lib.pdg_wgrad_reduce_batch(n, (VP * n)(*[_p(j[0]) for j in jb]), (IA * n)(*[j[1] for j in jb]),
-                                       (VP * n)(*[_p(j[2]) for j in jb]), (IA * n)(*[j[3] for j in jb]),
-                                       (IA * n)(*[j[4] for j in jb]), (VP * n)(*[_p(j[5]) for j in jb]), s)
+            lib.pdg_wgrad_reduce_batch(len(jb), _arr(VP, (_p(j[0]) for j in jb)), _arr(IA, (j[1] for j in jb)),
+                                       _arr(VP, (_p(j[2]) for j in jb)), _arr(IA, (j[3] for j in jb)),
+                                       _arr(IA, (j[4] for j in jb)), _arr(VP, (_p(j[5]) for j in jb)), b.s)
         jb = reds[:16]
-        n = len(jb)
         names = ("processor.node_net.4", "processor.edge_net.4", "node_encoder.4", "edge_encoder.4")
-        m = len(epi_narrow)
-        lib.pdg_bwd_epilogue(n, (VP * n)(*[_p(j[0]) for j in jb]), (IA * n)(*[j[1] for j in jb]),
-                             (VP * n)(*[_p(j[2]) for j in jb]), (IA * n)(*[j[3] for j in jb]),
-                             (IA * n)(*[j[4] for j in jb]), (VP * n)(*[_p(j[5]) for j in jb]),
-                             4, (VP * 4)(*[_p(acc[i]) for i in range(4)]), (IA * 4)(*([self._acc_rows] * 4)),
-                             (VP * 4)(*[_p(G[k + ".weight"]) for k in names]),
-                             (VP * 4)(*[_p(G[k + ".bias"]) for k in names]),
-                             m, (VP * m)(*[_p(j[0]) for j in epi_narrow]), (IA * m)(*[j[1] for j in epi_narrow]),
-                             (IA * m)(*[j[2] for j in epi_narrow]), (IA * m)(*[j[3] for j in epi_narrow]),
-                             (VP * m)(*[_p(j[4]) for j in epi_narrow]), (VP * m)(*[_p(j[5]) for j in epi_narrow]),
-                             (VP * m)(*[_p(j[6]) for j in epi_narrow]),
-                             _p(epi_enc[0]) if epi_enc else None, epi_enc[1] if epi_enc else 0,
-                             _p(epi_enc[2]) if epi_enc else None, _p(epi_enc[3]) if epi_enc else None, s)
+        lib.pdg_bwd_epilogue(len(jb), _arr(VP, (_p(j[0]) for j in jb)), _arr(IA, (j[1] for j in jb)),
+                             _arr(VP, (_p(j[2]) for j in jb)), _arr(IA, (j[3] for j in jb)),
+                             _arr(IA, (j[4] for j in jb)), _arr(VP, (_p(j[5]) for j in jb)),
+                             4, _arr(VP, (_p(a) for a in b.accs)), _arr(IA, [self._acc_rows] * 4),
+                             _arr(VP, (_p(G[k + ".weight"]) for k in names)),
+                             _arr(VP, (_p(G[k + ".bias"]) for k in names)),
+                             len(narrow), _arr(VP, (_p(j[0]) for j in narrow)), _arr(IA, (j[1] for j in narrow)),
+                             _arr(IA, (j[2] for j in narrow)), _arr(IA, (j[3] for j in narrow)),
+                             _arr(VP, (_p(j[4]) for j in narrow)), _arr(VP, (_p(j[5]) for j in narrow)),
+                             _arr(VP, (_p(j[6]) for j in narrow)),
+                             _p(enc[0]) if enc else None, enc[1] if enc else 0,
+                             _p(enc[2]) if enc else None, _p(enc[3]) if enc else None, b.s)

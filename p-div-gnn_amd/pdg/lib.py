@@ -34,7 +34,7 @@ def source_hash(csrc: Path = CSRC) -> str | None:
 P = c_void_p
 I = c_int
 
-# name -> argtypes (restype is int status unless listed in _RESTYPES)
+# name -> argtypes (the result is an int status unless the entry point is listed in _RESTYPES)
 SIGNATURES: dict[str, list] = {
     "pdg_last_error": [],
     "pdg_version": [],
@@ -116,13 +116,17 @@ SIGNATURES: dict[str, list] = {
     "pdg_node_labels": [I, P, I, I, P, P, P, P, ctypes.c_long, P],
     "pdg_p1_div_operator": [I, P, I, I, P, P, P, P, ctypes.c_long, P, P, P, ctypes.c_long, P],
 }
-_RESTYPES = {"pdg_last_error": ctypes.c_char_p, "pdg_source_hash": ctypes.c_char_p, "pdg_mesh_graph_scratch_bytes": ctypes.c_long,
-             "pdg_graph_plan_scratch_bytes": ctypes.c_long, "pdg_mesh_fields_scratch_bytes": ctypes.c_long}
+# the entry points that return a value, not a status: called as they are (no error check, not counted in
+# lib.calls, not passed to lib.hook)
+_RESTYPES = {"pdg_last_error": ctypes.c_char_p, "pdg_source_hash": ctypes.c_char_p,
+             "pdg_mesh_graph_scratch_bytes": ctypes.c_long, "pdg_graph_plan_scratch_bytes": ctypes.c_long,
+             "pdg_mesh_fields_scratch_bytes": ctypes.c_long,
+             "pdg_version": c_int, "pdg_max_blocks": c_int, "pdg_wgrad_slabs_per_cu": c_int, "pdg_pq_layout": c_int}
 
 LN_STAT_BYTES = 40   # sizeof(pdg_ln_stat)
+LN_BWD_BYTES = 24    # sizeof(pdg_ln_bwd)
 # PDG_DEBUG_SYNC=1: synchronise after every library call and name it on stderr (locating a faulting kernel)
 _DEBUG_SYNC = os.environ.get("PDG_DEBUG_SYNC") == "1"
-LN_BWD_BYTES = 24    # sizeof(pdg_ln_bwd)
 
 
 class PdgError(RuntimeError):
@@ -159,7 +163,7 @@ class _Lib:
         if not name.startswith("pdg_"):
             raise AttributeError(name)
         fn = getattr(self.load(), name)
-        if name in _RESTYPES or name in ("pdg_version", "pdg_max_blocks", "pdg_wgrad_slabs_per_cu", "pdg_pq_layout"):
+        if name in _RESTYPES:
             return fn
 
         def call(*args):

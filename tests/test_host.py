@@ -102,6 +102,6 @@ def test_kernel_variants_need_explicit_ab_opt_in(monkeypatch):
     with pytest.raises(ValueError):
         kernel_variants()
     monkeypatch.delenv("PDG_PAIR_BLOCKS_PER_CU")
-    assert kernel_variants({"nbwd_coop": False})["nbwd_coop"] is False
+    assert kernel_variants({"coop_fwd": False})["coop_fwd"] is False
     with pytest.raises(KeyError):
         kernel_variants({"no_such_variant": 1})
