@@ -150,6 +150,21 @@ __device__ __forceinline__ float div_den(float x, float den, float rstd) {
   return fmaf(r, rstd, q);
 }
 
+// LN(x) [+ r] for 4 features: the one form of the LayerNorm-apply (+ residual) formula, so every kernel
+// that states "bitwise the rows of" another forms them here (models.py:225 residual).
+template <bool RES>
+__device__ __forceinline__ f32x4 ln_res4(const f32x4& x, const f32x4& r, const LNStat& st, const f32x4& g,
+                                         const f32x4& b) {
+  f32x4 y;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float v = div_den(x[j] - st.mean, st.den, st.rstd) * g[j] + b[j];
+    if (RES) v += r[j];
+    y[j] = v;
+  }
+  return y;
+}
+
 // Copy a 128x128 block W[o][col0 + k] (row stride ld floats) into LDS, row stride WPAD.
 __device__ __forceinline__ void load_wblock(float* __restrict__ lds, const float* __restrict__ W,
                                             int ld, int col0) {
@@ -488,6 +503,15 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* red) {
   if (threadIdx.x == 0) {
     a = 0; b = 0;
     for (int i = 0; i < nw; ++i) { a += red[2 * i]; b += red[2 * i + 1]; }
+  }
+}
+
+// The block's LayerNorm partial pair (sum, sum of squares) -> part[2 b], part[2 b + 1].
+__device__ __forceinline__ void write_block_partials(double s1, double s2, double* red, double* __restrict__ part) {
+  block_sum2(s1, s2, red);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = s1;
+    part[2 * blockIdx.x + 1] = s2;
   }
 }
 

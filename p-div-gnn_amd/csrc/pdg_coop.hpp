@@ -213,4 +213,21 @@ __device__ __forceinline__ void slab_accumulate(float* __restrict__ slab, const 
 constexpr int EFC_TILE = X6_ROWS * OT_STRIDE;   // floats per fp32 row tile
 constexpr int EFC_ES = L + 8;                    // e tile row stride: the C operand reads are conflict free
 
+// ---- the per-element code the forward kernels of pdg_efwd.hip share (with ln_res4 and write_block_partials,
+// pdg_common.hpp): a formula two kernels must agree on bitwise is written once, here.
+
+// relu(d + b) for 4 features.
+__device__ __forceinline__ f32x4 bias_relu4(f32x4 d, f32x4 b) {
+  f32x4 a;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) a[j] = fmaxf(d[j] + b[j], 0.f);
+  return a;
+}
+
+// The LayerNorm partials of 4 features of one row: fp32 pair sums in this association, fp64 across.
+__device__ __forceinline__ void ln_partial_add(f32x4 a, double& s1, double& s2) {
+  s1 += (double)((a[0] + a[1]) + (a[2] + a[3]));
+  s2 += (double)((a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]));
+}
+
 }  // namespace

@@ -950,15 +950,13 @@ extern "C" int pdg_edge_gout_wc(int n_edges, const float* gC, const float* e, co
   const size_t shm_ln = 16384 + ((size_t)EBW_THREADS / 32 + 2) * 2 * L * sizeof(double);
   const size_t shm = shm_pipe > shm_ln ? shm_pipe : shm_ln;
   hipStream_t s = (hipStream_t)stream;
-#define PDG_GO2(R, LNF)                                                                                       \
-  hipLaunchKernelGGL((edge_gout_wc_kernel<R, LNF>), dim3(nslabs), dim3(EBW_THREADS), shm, s, gC, e, ge_next,   \
-                     WcT, ge_out, slabs, a2ln, st_ln, ln_partials, n_edges, ln_g, pairs, accumulate, slab_init)
-  if (ge_next) {
-    if (a2ln) PDG_GO2(true, true); else PDG_GO2(true, false);
-  } else {
-    if (a2ln) PDG_GO2(false, true); else PDG_GO2(false, false);
-  }
-#undef PDG_GO2
+  dispatch_bools(
+      [&](auto R, auto LNF) {
+        hipLaunchKernelGGL((edge_gout_wc_kernel<decltype(R)::value, decltype(LNF)::value>), dim3(nslabs),
+                           dim3(EBW_THREADS), shm, s, gC, e, ge_next, WcT, ge_out, slabs, a2ln, st_ln, ln_partials,
+                           n_edges, ln_g, pairs, accumulate, slab_init);
+      },
+      ge_next != nullptr, a2ln != nullptr);
   PDG_CHECK_LAUNCH("pdg_edge_gout_wc");
   return PDG_OK;
 }
@@ -1171,17 +1169,16 @@ extern "C" int pdg_gemm_sum2_coop(int rows, const float* in0, const float* in1, 
   const size_t pipe = 4 * IMG16 + (size_t)2 * R16 * OT_STRIDE * sizeof(float);
   const size_t cols = ((size_t)EBW_THREADS / 32 + 2) * 2 * L * sizeof(double);
   hipStream_t s = (hipStream_t)stream;
-#define PDG_GS2(C, R)                                                                                          \
-  hipLaunchKernelGGL((gemm_sum2_coop_kernel<C, R>), dim3(nblocks), dim3(EBW_THREADS), C ? (pipe > cols ? pipe : cols) \
-                     : pipe, s, rows, in0, in1, W0T, W1T, res, out, ln_a2, ln_st, partials, ln_g, pairs, accumulate)
-  if (partials) {
-    PDG_CHECK_ARG(ln_a2 && ln_st && PDG_ALIGNED(ln_a2) && (!pairs || ln_g),
-                  "pdg_gemm_sum2_coop: column partials need an aligned ln_a2, ln_st (and ln_g for pairs)");
-    if (res) PDG_GS2(true, true); else PDG_GS2(true, false);
-  } else {
-    if (res) PDG_GS2(false, true); else PDG_GS2(false, false);
-  }
-#undef PDG_GS2
+  PDG_CHECK_ARG(!partials || (ln_a2 && ln_st && PDG_ALIGNED(ln_a2) && (!pairs || ln_g)),
+                "pdg_gemm_sum2_coop: column partials need an aligned ln_a2, ln_st (and ln_g for pairs)");
+  dispatch_bools(
+      [&](auto C, auto R) {
+        constexpr bool COLS = decltype(C)::value;
+        hipLaunchKernelGGL((gemm_sum2_coop_kernel<COLS, decltype(R)::value>), dim3(nblocks), dim3(EBW_THREADS),
+                           COLS ? (pipe > cols ? pipe : cols) : pipe, s, rows, in0, in1, W0T, W1T, res, out, ln_a2,
+                           ln_st, partials, ln_g, pairs, accumulate);
+      },
+      partials != nullptr, res != nullptr);
   PDG_CHECK_LAUNCH("pdg_gemm_sum2_coop");
   return PDG_OK;
 }

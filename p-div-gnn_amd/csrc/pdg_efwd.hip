@@ -103,13 +103,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_fwd_coop_kernel(
     for (int u = 0; u < 2; ++u) {
       const int r = rg + 16 * u;
       const bool ok = base + r < r1;
-      f32x4 e;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {   // ln_apply (pdg_fwd.hip), element by element
-        float y = div_den(xa[u][j] - st.mean, st.den, st.rstd) * g4[j] + bb4[j];
-        if (RES) y += xr[u][j];
-        e[j] = y;
-      }
+      const f32x4 e = ln_res4<RES>(xa[u], xr[u], st, g4, bb4);
       rows_store4_nt(rs_e, base + r - r0, 4 * cg, e);
       img_store4(img_e, r, cg, ok ? e : f32x4{0.f, 0.f, 0.f, 0.f});
     }
@@ -243,18 +237,8 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_fwd_coop_kernel(
   }
   double* red = reinterpret_cast<double*>(sm);
   __syncthreads();
-  block_sum2(sm1, sm2, red);
-  if (threadIdx.x == 0) {
-    part_m[2 * blockIdx.x] = sm1;
-    part_m[2 * blockIdx.x + 1] = sm2;
-  }
-  if (EU) {
-    block_sum2(se1, se2, red + 32);
-    if (threadIdx.x == 0) {
-      part_e[2 * blockIdx.x] = se1;
-      part_e[2 * blockIdx.x + 1] = se2;
-    }
-  }
+  write_block_partials(sm1, sm2, red, part_m);
+  if (EU) write_block_partials(se1, se2, red + 32, part_e);
 }
 
 // ============================================================================ edge forward, inference
@@ -333,7 +317,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_fwd_infer_kernel(
     const bool ok = base + rg < r1;
     f32x4 e;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {   // ln_apply (pdg_fwd.hip), element by element
+    for (int j = 0; j < 4; ++j) {   // ln_res4 (pdg_common.hpp) written out: the call changed this kernel's ISA
       float y = div_den(xa[s][j] - st.mean, st.den, st.rstd) * g4[j] + bb4[j];
       if (RES) y += xr[s][j];
       e[j] = y;
@@ -390,9 +374,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_fwd_infer_kernel(
       const bool ok = k > 0 && basep + pr < r1;
 #pragma unroll
       for (int u = 0; u < NI; ++u) {
-        f32x4 a;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] = fmaxf(d2[u][0][j] + b2o[j], 0.f);
+        const f32x4 a = bias_relu4(d2[u][0], b2o);
         *reinterpret_cast<f32x4*>(t_a2 + (2 * sp + u) * EP_TILE + pr * OT_STRIDE + oc) = a;
         if (ok) {
           const double p1 = (double)((a[0] + a[1]) + (a[2] + a[3]));
@@ -445,18 +427,8 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_fwd_infer_kernel(
   }
   double* red = reinterpret_cast<double*>(sm);
   __syncthreads();
-  block_sum2(sm1, sm2, red);
-  if (threadIdx.x == 0) {
-    part_m[2 * blockIdx.x] = sm1;
-    part_m[2 * blockIdx.x + 1] = sm2;
-  }
-  if (EU) {
-    block_sum2(se1, se2, red + 32);
-    if (threadIdx.x == 0) {
-      part_e[2 * blockIdx.x] = se1;
-      part_e[2 * blockIdx.x + 1] = se2;
-    }
-  }
+  write_block_partials(sm1, sm2, red, part_m);
+  if (EU) write_block_partials(se1, se2, red + 32, part_e);
 }
 
 // ============================================================================ edge encoder forward
@@ -520,14 +492,9 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_enc_fwd_kernel(
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
       const int r = 16 * nb + (l & 15);
-      f32x4 a;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[j] = fmaxf(d[0][nb][j] + b2o[j], 0.f);
+      const f32x4 a = bias_relu4(d[0][nb], b2o);
       *reinterpret_cast<f32x4*>(t_a + r * OT_STRIDE + oc) = a;
-      if (base + r < r1) {
-        s1 += (double)((a[0] + a[1]) + (a[2] + a[3]));
-        s2 += (double)((a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]));
-      }
+      if (base + r < r1) ln_partial_add(a, s1, s2);
     }
     __syncthreads();   // the a2 tile is complete; the image is free
 #pragma unroll
@@ -623,14 +590,9 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void node_enc_fwd_kernel(
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
       const int r = 16 * nb + (l & 15);
-      f32x4 a;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[j] = fmaxf(d[nb][j] + b2o[j], 0.f);
+      const f32x4 a = bias_relu4(d[nb], b2o);
       *reinterpret_cast<f32x4*>(t_a + r * OT_STRIDE + oc) = a;
-      if (base + r < r1) {
-        s1 += (double)((a[0] + a[1]) + (a[2] + a[3]));
-        s2 += (double)((a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]));
-      }
+      if (base + r < r1) ln_partial_add(a, s1, s2);
     }
     __syncthreads();   // the a2 tile is complete; the image is free
 #pragma unroll
@@ -652,7 +614,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void node_enc_fwd_kernel(
 
 // ============================================================================ decoder forward
 // The node decoder (models.py:316-321: x_S = LN(a2_prev) + x_prev, a1d = relu(Wd1 x_S + bd1),
-// y = Wd2 a1d + bd2, unscaled when asked) in the layout of node_enc_fwd_kernel: x_S element by element as
+// y = Wd2 a1d + bd2, unscaled when asked) in the layout of node_enc_fwd_kernel: x_S by ln_res4, as
 // ln_res_frag forms it (bitwise), Wd1 x_S as an unbiased bf16x6 product from registers (decoder_kernel: fp32
 // MFMAs from an LDS weight copy), a1d rows through an fp32 tile, the 3 outputs of a row as fp32 dot products
 // over the tile (96 threads, features in order).  part != NULL: the last node LayerNorm's statistics reduced
@@ -716,13 +678,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void decoder_coop_kernel(
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = rg + 16 * u;
-      f32x4 x;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {   // ln_res_frag, element by element
-        float v = div_den(xa[u][j] - st.mean, st.den, st.rstd) * gg[j] + bb[j];
-        v += xr[u][j];
-        x[j] = v;
-      }
+      const f32x4 x = ln_res4<true>(xa[u], xr[u], st, gg, bb);
       const bool ok = base + r < r1;
       rows_store4_nt(rs_x, base + r - r0, 4 * cg, x);
       img_store4(img, r, cg, ok ? x : f32x4{0.f, 0.f, 0.f, 0.f});
@@ -734,10 +690,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void decoder_coop_kernel(
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
       const int r = 16 * nb + (l & 15);
-      f32x4 a;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a[j] = fmaxf(d[nb][j] + b1o[j], 0.f);
-      *reinterpret_cast<f32x4*>(t_a + r * OT_STRIDE + oc) = a;
+      *reinterpret_cast<f32x4*>(t_a + r * OT_STRIDE + oc) = bias_relu4(d[nb], b1o);
     }
     __syncthreads();   // the a1d tile is complete; the image is free
 #pragma unroll
@@ -821,25 +774,13 @@ extern "C" int pdg_edge_fwd_coop(int n_edges, const float* a2_prev, const pdg_ln
   const size_t shm = 2 * EBW_IMG + 2 * EFC_TILE * sizeof(float) + EBW_IMG + 2 * EFC_TILE * sizeof(float) +
                      2 * EBW_WAVES * 64 * 16;
   hipStream_t s = (hipStream_t)stream;
-#define PDG_EFC_X(R, U, X)                                                                                    \
-  hipLaunchKernelGGL((edge_fwd_coop_kernel<R, U, X>), dim3(nblocks), dim3(EBW_THREADS), shm, s,               \
-                     n_edges, a2_prev, st, ln_g, ln_b, e_res, e_out, src, dst, P, Q, W1, b1, W2, b2, a1m, a2m, a1e,   \
-                     a2e, part_m, part_e)
-#define PDG_EFC(R, U)            \
-  do {                           \
-    if (xcd) {                   \
-      PDG_EFC_X(R, U, true);     \
-    } else {                     \
-      PDG_EFC_X(R, U, false);    \
-    }                            \
-  } while (0)
-  if (e_res) {
-    if (with_edge_update) PDG_EFC(true, true); else PDG_EFC(true, false);
-  } else {
-    if (with_edge_update) PDG_EFC(false, true); else PDG_EFC(false, false);
-  }
-#undef PDG_EFC
-#undef PDG_EFC_X
+  dispatch_bools(
+      [&](auto R, auto U, auto X) {
+        hipLaunchKernelGGL((edge_fwd_coop_kernel<decltype(R)::value, decltype(U)::value, decltype(X)::value>),
+                           dim3(nblocks), dim3(EBW_THREADS), shm, s, n_edges, a2_prev, st, ln_g, ln_b, e_res, e_out,
+                           src, dst, P, Q, W1, b1, W2, b2, a1m, a2m, a1e, a2e, part_m, part_e);
+      },
+      e_res != nullptr, with_edge_update != 0, xcd);
   PDG_CHECK_LAUNCH("pdg_edge_fwd_coop");
   return PDG_OK;
 }
@@ -863,24 +804,13 @@ extern "C" int pdg_edge_fwd_infer(int n_edges, const float* a2_prev, const pdg_l
   const bool xcd = nblocks == XCD_GRID;
   const size_t shm = 6 * IMG16 + 4 * EP_TILE * sizeof(float) + 2 * EBW_WAVES * 64 * 16;
   hipStream_t s = (hipStream_t)stream;
-#define PDG_EI_X(R, U, X)                                                                                     \
-  hipLaunchKernelGGL((edge_fwd_infer_kernel<R, U, X>), dim3(nblocks), dim3(EBW_THREADS), shm, s, n_edges, a2_prev, \
-                     st, ln_g, ln_b, e_res, e_out, src, dst, P, Q, W1, b1, W2, b2, a2m, a2e, part_m, part_e)
-#define PDG_EI(R, U)             \
-  do {                           \
-    if (xcd) {                   \
-      PDG_EI_X(R, U, true);      \
-    } else {                     \
-      PDG_EI_X(R, U, false);     \
-    }                            \
-  } while (0)
-  if (e_res) {
-    if (with_edge_update) PDG_EI(true, true); else PDG_EI(true, false);
-  } else {
-    if (with_edge_update) PDG_EI(false, true); else PDG_EI(false, false);
-  }
-#undef PDG_EI
-#undef PDG_EI_X
+  dispatch_bools(
+      [&](auto R, auto U, auto X) {
+        hipLaunchKernelGGL((edge_fwd_infer_kernel<decltype(R)::value, decltype(U)::value, decltype(X)::value>),
+                           dim3(nblocks), dim3(EBW_THREADS), shm, s, n_edges, a2_prev, st, ln_g, ln_b, e_res, e_out,
+                           src, dst, P, Q, W1, b1, W2, b2, a2m, a2e, part_m, part_e);
+      },
+      e_res != nullptr, with_edge_update != 0, xcd);
   PDG_CHECK_LAUNCH("pdg_edge_fwd_infer");
   return PDG_OK;
 }

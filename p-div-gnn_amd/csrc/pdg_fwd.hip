@@ -97,11 +97,7 @@ __device__ __forceinline__ void accum_stats(const float (&v)[FRAG], bool valid, 
 
 __device__ __forceinline__ void write_partials(double s1, double s2, double* part) {
   __shared__ double red[2 * 16];
-  block_sum2(s1, s2, red);
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = s1;
-    part[2 * blockIdx.x + 1] = s2;
-  }
+  write_block_partials(s1, s2, red, part);
 }
 
 // v = LN(a2 row) [+ residual row], four fenced chunks of 8 floats.
@@ -121,13 +117,11 @@ __device__ __forceinline__ void ln_res_frag(float (&v)[FRAG], const float* __res
       bb[t] = ld4(b + lc, 2 * q + t);
     }
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < 2; ++t) {
+      const f32x4 y = ln_res4<RES>(x[t], r[t], st, gg[t], bb[t]);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float y = div_den(x[t][j] - st.mean, st.den, st.rstd) * gg[t][j] + bb[t][j];
-        if (RES) y += r[t][j];
-        v[8 * q + 4 * t + j] = y;
-      }
+      for (int j = 0; j < 4; ++j) v[8 * q + 4 * t + j] = y[j];
+    }
     PDG_FENCE();
   }
 }
@@ -496,18 +490,8 @@ __global__ __launch_bounds__(64 * EF_WAVES, EF_WAVES / 4) void edge_fwd_kernel(
 #undef PDG_GEMM_2
   // the weight images are dead once every wave has passed block_sum2's first barrier
   double* red = reinterpret_cast<double*>(lds);
-  block_sum2(sm1, sm2, red);
-  if (threadIdx.x == 0) {
-    part_m[2 * blockIdx.x] = sm1;
-    part_m[2 * blockIdx.x + 1] = sm2;
-  }
-  if (EU) {
-    block_sum2(se1, se2, red + 32);
-    if (threadIdx.x == 0) {
-      part_e[2 * blockIdx.x] = se1;
-      part_e[2 * blockIdx.x + 1] = se2;
-    }
-  }
+  write_block_partials(sm1, sm2, red, part_m);
+  if (EU) write_block_partials(se1, se2, red + 32, part_e);
 }
 
 extern "C" int pdg_edge_fwd(int n_edges, const float* a2_prev, const pdg_ln_stat* st, const float* ln_g,
@@ -527,15 +511,13 @@ extern "C" int pdg_edge_fwd(int n_edges, const float* a2_prev, const pdg_ln_stat
   const int grid = persistent_grid(n_edges, EF_WAVES, 1);
   const size_t shm = (size_t)EDGE_LDS_BYTES;
   hipStream_t s = (hipStream_t)stream;
-#define PDG_EDGE_FWD(R, U)                                                                                     \
-  hipLaunchKernelGGL((edge_fwd_kernel<R, U>), dim3(grid), dim3(64 * EF_WAVES), shm, s, n_edges, a2_prev, st, ln_g, ln_b, \
-                     e_res, e_out, src, dst, P, Q, W1, b1, W2, b2, a1m, a2m, a1e, a2e, part_m, part_e)
-  if (e_res) {
-    if (with_edge_update) PDG_EDGE_FWD(true, true); else PDG_EDGE_FWD(true, false);
-  } else {
-    if (with_edge_update) PDG_EDGE_FWD(false, true); else PDG_EDGE_FWD(false, false);
-  }
-#undef PDG_EDGE_FWD
+  dispatch_bools(
+      [&](auto R, auto U) {
+        hipLaunchKernelGGL((edge_fwd_kernel<decltype(R)::value, decltype(U)::value>), dim3(grid), dim3(64 * EF_WAVES),
+                           shm, s, n_edges, a2_prev, st, ln_g, ln_b, e_res, e_out, src, dst, P, Q, W1, b1, W2, b2, a1m,
+                           a2m, a1e, a2e, part_m, part_e);
+      },
+      e_res != nullptr, with_edge_update != 0);
   PDG_CHECK_LAUNCH("pdg_edge_fwd");
   if (nparts) *nparts = grid;
   return PDG_OK;

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(64 * NU_COMPUTE, 1) void node_net_x6_kernel(
     stage((i + 2) % 3);
   }
   __shared__ double red[2 * NU_COMPUTE];
-  block_sum2(s1, s2, red);
+  block_sum2(s1, s2, red);   // write_block_partials, written out: the call changed this kernel's ISA
   if (threadIdx.x == 0) {
     part[2 * blockIdx.x] = s1;
     part[2 * blockIdx.x + 1] = s2;
@@ -414,13 +414,7 @@ __device__ __forceinline__ void store_xt1(unsigned char* __restrict__ img, int t
                                           const f32x4& rv, const LNStat& st, const f32x4& gg, const f32x4& bb,
                                           float* __restrict__ xout) {
   const int j = threadIdx.x & 31, rr = threadIdx.x >> 5;
-  f32x4 y;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {   // ln_res_frag (pdg_fwd.hip), element by element
-    float v = div_den(av[e] - st.mean, st.den, st.rstd) * gg[e] + bb[e];
-    if (RES) v += rv[e];
-    y[e] = v;
-  }
+  const f32x4 y = ln_res4<RES>(av, rv, st, gg, bb);
   x6_store4<PQ_T16>(img, rr, j, y);
   rows_store4(tile_rsrc(xout, t, N), rr, 4 * j, y);
 }

@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/pdivgnn.h"
 
 namespace pdg {
@@ -31,6 +33,20 @@ constexpr int MAX_BLOCKS = 2048;
   } while (0)
 
 #define PDG_ALIGNED(p) ((((uintptr_t)(p)) & 15u) == 0)
+
+// f(std::bool_constant<b>{}...) for run-time bools: a launcher's generic lambda names its kernel once,
+// kernel<decltype(R)::value, ...>, and every combination of the template bools is instantiated.
+template <class F>
+inline void dispatch_bools(F&& f) {
+  f();
+}
+template <class F, class... Bs>
+inline void dispatch_bools(F&& f, bool b, Bs... rest) {
+  if (b)
+    dispatch_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+  else
+    dispatch_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
 
 // Wave tiles of 16 rows (pdg_common.hpp).
 __host__ __device__ inline int tiles_of(long rows) { return (int)((rows + 15) / 16); }

@@ -819,7 +819,7 @@ def test_transpose128_batch(env):
         assert torch.equal(o.cpu(), r.T.contiguous().cpu())
 
 
-@pytest.mark.parametrize("E,eu,res", [(1000, 1, 1), (4099, 0, 1), (77, 1, 0)])
+@pytest.mark.parametrize("E,eu,res", [(1000, 1, 1), (4099, 0, 1), (77, 1, 0), (1, 1, 1), (33, 0, 0)])
 def test_edge_fwd_coop_matches_edge_fwd(env, E, eu, res):
     """pdg_edge_fwd_coop (block-cooperative layout) against pdg_edge_fwd on the same inputs: e_t bitwise;
     the layer-1 outputs (C = Wc e an unbiased bf16x6 product in the coop kernel, fp32 MFMAs in pdg_edge_fwd)
@@ -1350,7 +1350,7 @@ def test_edge_gout_wc_vs_fp64(env, E, nb, res, ln, acc):
 
 
 
-@pytest.mark.parametrize("E,nb", [(77, 37), (4099, 37), (30011, 256), (100000, 256)])
+@pytest.mark.parametrize("E,nb", [(77, 37), (4099, 37), (30011, 256), (100000, 256), (1, 1), (33, 2), (33, 256)])
 @pytest.mark.parametrize("eu,res", [(1, 1), (0, 1), (1, 0), (0, 0)])
 def test_edge_fwd_infer_matches_coop(env, E, nb, eu, res):
     """pdg_edge_fwd_infer (inference: 16-row rounds, one barrier per round, the C product of round k beside the
