@@ -371,6 +371,30 @@ int pdg_edge_enc_bwd(int n_edges, const float* gy, const float* a2, const float*
                      const float* b0, const pdg_ln_stat* st, const pdg_ln_bwd* lb, const double* lb_pairs,
                      int lb_npairs, const float* ln_g, const float* W2T, float* slabs, double* narrow_sums,
                      int nslabs, int slab_init, void* stream);
+/* Input gradients of the encoders (pdg_ingrad.hip): the vector-Jacobian product of the forward with respect
+ * to the mesh inputs, one product past where pdg_edge_enc_bwd / pdg_mlp2_bwd_coop stop.  Both take the
+ * operands of those calls (gy = d loss / d e_0 or x_0, a2, st, lb / lb_pairs, ln_g, W2T) and form, per row,
+ *   gz2 = LN_bwd(gy) [a2 > 0],  u = W2T gz2,  g_in[c] = sum_j W0[j][c] [a1[j] > 0] u[j]
+ * (models.py:260-274 backwards, the W2T product in bf16x6), then undo the input formatting of
+ * pdg_format_inputs (models.py:140-162; stats8 and scale_input as there: / std when scale_input).
+ * nblocks blocks of 512 threads, contiguous row ranges; deterministic, no scratch.
+ *   pdg_edge_enc_gin: a1 = w0 e_in + b0 recomputed from the scalar input (plan order);
+ *                     g_edge_attr[perm[k]] = g_in of plan row k (the caller's edge order, n_edges floats).
+ *   pdg_node_enc_gin: a1 as stored by the forward, W0 = node_encoder.0.weight (128 x 6); columns 0-2 go to
+ *                     g_mean_stress (n_nodes x 3), 3-4 to g_pos (n_nodes x 2); column 5 (the integer
+ *                     node type) gets no gradient. */
+int pdg_edge_enc_gin(int n_edges, const float* gy, const float* a2, const float* e_in, const float* w0,
+                     const float* b0, const pdg_ln_stat* st, const pdg_ln_bwd* lb, const double* lb_pairs,
+                     int lb_npairs, const float* ln_g, const float* W2T, const int* perm, const float* stats8,
+                     int scale_input, float* g_edge_attr, int nblocks, void* stream);
+int pdg_node_enc_gin(int n_nodes, const float* gy, const float* a2, const float* a1, const float* W0,
+                     const pdg_ln_stat* st, const pdg_ln_bwd* lb, const double* lb_pairs, int lb_npairs,
+                     const float* ln_g, const float* W2T, const float* stats8, int scale_input,
+                     float* g_mean_stress, float* g_pos, int nblocks, void* stream);
+/* out[g][c] = sum of rows[ptr[g] .. ptr[g + 1])[c], c < 3: the gradient with respect to a graph's imposed
+ * mean stress when it is broadcast to every node (benchmark_gnn_fem.py:404-407) from the per-node
+ * g_mean_stress.  One block per graph, fp64 in a fixed order, rounded once; an empty graph gets zeros. */
+int pdg_graph_colsum3(int n_graphs, const int* ptr, const float* rows, float* out, void* stream);
 /* grad_w0 += sum_b narrow_sums[b][0:128], grad_b0 += sum_b narrow_sums[b][128:256] (block order). */
 int pdg_enc_narrow_reduce(const double* narrow_sums, int nslabs, float* grad_w0, float* grad_b0, void* stream);
 int pdg_edge_gout_wc(int n_edges, const float* gC, const float* e, const float* ge_next,

@@ -166,6 +166,17 @@ class FwdCtx:
 
 
 @dataclass
+class InputGrads:
+    """The output buffers of the backward's opt-in input gradients (EPDEngine.backward, input_grads): fp32,
+    contiguous, every element written.  ``stats8`` / ``scale_input`` as the forward took them."""
+    mean_stress: torch.Tensor   # (N, 3)
+    pos: torch.Tensor           # (N, 2)
+    edge_attr: torch.Tensor     # (E,), in the caller's edge order
+    stats8: torch.Tensor
+    scale_input: bool
+
+
+@dataclass
 class _Fwd:
     """What one phase of the forward hands the next."""
     s: int                      # stream handle
@@ -538,8 +549,11 @@ class EPDEngine:
                                    _arr(VP, (j[2] for j in jobs)), s)
         return out
 
-    def backward(self, P: dict, ctx: FwdCtx, gy: torch.Tensor, G: dict) -> None:
-        """Accumulate d(loss)/d(param) into G[name] (fp32, same shapes as P).
+    def backward(self, P: dict, ctx: FwdCtx, gy: torch.Tensor, G: dict,
+                 input_grads: InputGrads | None = None) -> None:
+        """Accumulate d(loss)/d(param) into G[name] (fp32, same shapes as P).  With ``input_grads``, also
+        write d(loss)/d(mean_stress, pos, edge_attr) into its buffers (two more launches, next to the
+        encoders' backward; the default launch sequence is unchanged).
 
         The input-gradient chain runs step by step (reverse order); the weight
         gradients of the shared 128x128 blocks are deferred: every step's row
@@ -549,7 +563,7 @@ class EPDEngine:
         self._bwd_decoder(P, ctx, b, gy)
         for t in reversed(range(ctx.steps)):
             self._bwd_step(P, ctx, b, t)
-        self._bwd_encoders(P, ctx, b)
+        self._bwd_encoders(P, ctx, b, input_grads)
         self._bwd_wgrads(b)
         self._bwd_epilogue(b)
 
@@ -718,13 +732,18 @@ class EPDEngine:
             self._t("edge_gout", lib.pdg_edge_gout_wc, E, _p(gC), _p(d["e"]), _p(b.ge_next), _p(T["WcT"]),
                     _p(ge_out), _p(b.slabs_wc), nse, _p(a2ln), st_ln, _p(acc), _p(gl), _p(pp), 1, last, s)
 
-    def _bwd_encoders(self, P, ctx: FwdCtx, b: _Bwd) -> None:
+    def _bwd_encoders(self, P, ctx: FwdCtx, b: _Bwd, ig: InputGrads | None = None) -> None:
         """The two encoders' backward; their narrow first-layer gradients go to the epilogue (fused) or
-        pdg_wgrad_narrow."""
+        pdg_wgrad_narrow.  With `ig`, the input gradients from the same operands (pdg_node_enc_gin /
+        pdg_edge_enc_gin, each issued before the call whose operands it shares)."""
         N, E, T, G, s, nse = ctx.plan.n_nodes, ctx.plan.n_edges, b.T, b.G, b.s, self._nslabs_e
         gz2 = self._empty(N, L)
         _, pp, a2, st_ln, gl = self._ln_producing(P, ctx, b, "n", 0)
         pn, nn = self._pairs_src(b, pp, b.n_node)
+        if ig is not None:
+            self._t("node_enc_gin", lib.pdg_node_enc_gin, N, _p(b.gx_next), _p(a2), _p(ctx.a1_ne),
+                    _p(P["node_encoder.0.weight"]), st_ln, None, pn, nn, _p(gl), _p(T["Wne2T"]), _p(ig.stats8),
+                    int(ig.scale_input), _p(ig.mean_stress), _p(ig.pos), nse, s)
         # bf16x6 (pdg_mlp2_bwd_coop), + the first layer's weight / bias gradient from gz1 and the encoder
         # input (block partials; gz1 is not stored)
         self._t("node_enc_bwd", lib.pdg_mlp2_bwd_coop, N, _p(b.gx_next), _p(a2), _p(ctx.a1_ne), st_ln, None,
@@ -736,6 +755,10 @@ class EPDEngine:
             return
         acc, pp, a2, st_ln, gl = self._ln_producing(P, ctx, b, "e", 0)
         pe, ne = self._edge_ln_pairs(ctx, b, pp, b.ge_next, a2, st_ln, acc, gl)
+        if ig is not None:   # the layer-1 output recomputed from e_in, whichever backward variant runs
+            self._t("edge_enc_gin", lib.pdg_edge_enc_gin, E, _p(b.ge_next), _p(a2), _p(ctx.e_in),
+                    _p(P["edge_encoder.0.weight"]), _p(P["edge_encoder.0.bias"]), st_ln, None, pe, ne, _p(gl),
+                    _p(T["Wee2T"]), _p(ctx.plan.perm), _p(ig.stats8), int(ig.scale_input), _p(ig.edge_attr), nse, s)
         if b.fused:   # one pass: weight gradients in slabs, the 1 -> 128 layer's as per-block sums
             nsum = torch.empty(nse, 2 * L, dtype=torch.float64, device=self.device)
             self._t("edge_enc_bwd", lib.pdg_edge_enc_bwd, E, _p(b.ge_next), _p(a2), _p(ctx.e_in),

@@ -90,6 +90,9 @@ SIGNATURES: dict[str, list] = {
     "pdg_wgrad_slabs_per_cu": [],
     "pdg_wgrad_pairs": [I, P, P, P, P, I, P, P, I, P],
     "pdg_edge_enc_bwd": [I, P, P, P, P, P, P, P, P, I, P, P, P, P, I, I, P],
+    "pdg_edge_enc_gin": [I, P, P, P, P, P, P, P, P, I, P, P, P, P, I, P, I, P],
+    "pdg_node_enc_gin": [I, P, P, P, P, P, P, P, I, P, P, P, I, P, P, I, P],
+    "pdg_graph_colsum3": [I, P, P, P, P],
     "pdg_enc_narrow_reduce": [P, I, P, P, P],
     "pdg_edge_bwd_w2": [I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, P, I, I, P],
     "pdg_edge_gout_wc": [I, P, P, P, P, P, P, I, P, P, P, P, P, I, I, P],
