@@ -395,6 +395,64 @@ int pdg_node_enc_gin(int n_nodes, const float* gy, const float* a2, const float*
  * mean stress when it is broadcast to every node (benchmark_gnn_fem.py:404-407) from the per-node
  * g_mean_stress.  One block per graph, fp64 in a fixed order, rounded once; an empty graph gets zeros. */
 int pdg_graph_colsum3(int n_graphs, const int* ptr, const float* rows, float* out, void* stream);
+/* ---------------------------------------------------------------- tangent pass (pdg_tangent.hip)
+ * The Jacobian-vector product of the forward with respect to the formatted inputs, (dx_in (N x 6), de_in (E))
+ * -> d local_stress (N x 3), linearised at the activations a need_grad forward keeps: biases drop out, a relu
+ * is a multiplication by the stored mask [a > 0], residuals add the previous tangent, and a graph LayerNorm
+ * y = g (a - mu) / (sigma + eps) + b over n = rows x 128 elements becomes
+ *   dLN = g ((da - T1 / n) / (sigma + eps) - (a - mu) T2 / (n sigma (sigma + eps)^2)),
+ *   T1 = sum da, T2 = sum (a - mu) da over all n elements.
+ * Every kernel that produces a pre-LayerNorm tangent da writes nblocks fp64 pairs (T1, T2) (`partials`, one per
+ * block, every entry written); its consumer takes them as `pairs` / `npairs` (16-byte aligned) with the
+ * LayerNorm's forward statistics `st` and reduces them itself in a fixed order: no atomics, no launch in
+ * between, bitwise reproducible.  All 128 x 128 products are unbiased bf16x6 MFMA products.  nblocks blocks of
+ * 512 threads over contiguous row ranges, 1 .. pdg_max_blocks(); rows per call below 2^22; launches only
+ * (no allocation, no synchronisation, capturable).  Weights are the nn.Linear (out x in) arrays of the forward.
+ *
+ *   pdg_node_enc_tan   da2 = [a2 > 0] W2 [a1 > 0] W0 dx_in          (W0 128 x 6; a1, a2 as stored)
+ *   pdg_edge_enc_tan   da2 = [a2 > 0] W2 [w0 e_in + b0 > 0] w0 de_in (the first layer's sign recomputed as
+ *                      fma(w0, e_in, 0) + b0 > 0, pdg_edge_enc_bwd's form); plan order
+ *   pdg_node_pre_tan   dx_out = dLN(da2_prev) [+ dx_res], dP = Wa dx_out, dQ = Wb dx_out (W1 = edge_net.0's
+ *                      128 x 384 weight; dP, dQ plain N x 128 arrays)
+ *   pdg_edge_tan       de_out = dLN(da2_prev) [+ de_res], C = Wc de_out;
+ *                      da2m = [a2m > 0] W2 [a1m > 0] (C + dP[dst] + dQ[src]), part_m;
+ *                      with_edge_update: da2e = [a2e > 0] W2 [a1e > 0] (C + dP[src] + dQ[dst]), part_e
+ *                      (st_m / st_e: the forward statistics of a2m / a2e; endpoints clamped to n_nodes)
+ *   pdg_segment_sum_tan daggr[n] = g sum_{k in rowptr[n] .. rowptr[n + 1])} dLN(da2m[k]) without the weight,
+ *                      in edge order
+ *   pdg_node_net_tan   da2n = [a2n > 0] W2 [a1n > 0] (W1[:, :128] daggr + W1[:, 128:] dx)   (W1 128 x 256)
+ *   pdg_decoder_tan    dy = Wd2 [a1d > 0] Wd1 (dLN(da2_prev) [+ dx_res]) [* std_out[0], the output's
+ *                      standard deviation (one float), with scale_output]
+ *   pdg_edge_len_tan   dlen[k] = (pos[s] - pos[d]) . (dpos[s] - dpos[d]) / edge_attr[k] where edge_attr[k] > 0
+ *                      and both endpoints lie in 0 .. n_nodes - 1, else 0 (periodic pairs, coincident nodes:
+ *                      a constant length 0); s, d = src[k], dst[k] in the caller's edge order; fp64, rounded once. */
+int pdg_node_enc_tan(int n_nodes, const float* dx_in, const float* a1, const float* W0, const float* W2,
+                     const float* a2, const pdg_ln_stat* st, float* da2, double* partials, int nblocks,
+                     void* stream);
+int pdg_edge_enc_tan(int n_edges, const float* de_in, const float* e_in, const float* w0, const float* b0,
+                     const float* W2, const float* a2, const pdg_ln_stat* st, float* da2, double* partials,
+                     int nblocks, void* stream);
+int pdg_node_pre_tan(int n_nodes, const float* da2_prev, const float* a2_prev, const pdg_ln_stat* st,
+                     const double* pairs, int npairs, const float* ln_g, const float* dx_res, float* dx_out,
+                     const float* W1, float* dP, float* dQ, int nblocks, void* stream);
+int pdg_edge_tan(int n_edges, int n_nodes, const float* da2_prev, const float* a2_prev, const pdg_ln_stat* st,
+                 const double* pairs, int npairs, const float* ln_g, const float* de_res, float* de_out,
+                 const int* src, const int* dst, const float* dP, const float* dQ, const float* W1, const float* W2,
+                 const float* a1m, const float* a2m, const pdg_ln_stat* st_m, const float* a1e, const float* a2e,
+                 const pdg_ln_stat* st_e, float* da2m, float* da2e, double* part_m, double* part_e,
+                 int with_edge_update, int nblocks, void* stream);
+int pdg_segment_sum_tan(int n_nodes, int n_edges, const int* rowptr, const float* da2m, const float* a2m,
+                        const pdg_ln_stat* st, const double* pairs, int npairs, const float* ln_g, float* daggr,
+                        int nblocks, void* stream);
+int pdg_node_net_tan(int n_nodes, const float* daggr, const float* dx, const float* W1, const float* W2,
+                     const float* a1n, const float* a2n, const pdg_ln_stat* st, float* da2n, double* partials,
+                     int nblocks, void* stream);
+int pdg_decoder_tan(int n_nodes, const float* da2_prev, const float* a2_prev, const pdg_ln_stat* st,
+                    const double* pairs, int npairs, const float* ln_g, const float* dx_res, const float* Wd1,
+                    const float* a1d, const float* Wd2, const float* std_out, int scale_output, float* dy,
+                    int nblocks, void* stream);
+int pdg_edge_len_tan(int n_edges, int n_nodes, const int64_t* src, const int64_t* dst, const float* pos,
+                     const float* dpos, const float* edge_attr, float* dlen, void* stream);
 /* grad_w0 += sum_b narrow_sums[b][0:128], grad_b0 += sum_b narrow_sums[b][128:256] (block order). */
 int pdg_enc_narrow_reduce(const double* narrow_sums, int nslabs, float* grad_w0, float* grad_b0, void* stream);
 int pdg_edge_gout_wc(int n_edges, const float* gC, const float* e, const float* ge_next,

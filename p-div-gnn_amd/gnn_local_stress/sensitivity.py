@@ -11,6 +11,14 @@ produces parameter gradients only); this module is the supported route:
 
 One forward and one backward of the engine (pdg.engine) with two more launches next to the encoders'
 backward (pdg_node_enc_gin, pdg_edge_enc_gin) and one per-graph reduction (pdg_graph_colsum3).
+
+The other direction, how the whole field moves when an input moves, is the Jacobian-vector product:
+
+    t = input_tangents(model, batch, d_load=...)          # t.local_stress, t.d_local_stress
+    A = localisation_tensor(model, batch)                 # A[n, i, j] = d sigma_i(n) / d Sigma_j
+
+One forward and one tangent pass per direction (pdg.engine.EPDEngine.tangent, csrc/pdg_tangent.hip): the
+forward linearised at its own stored activations, so the relu masks are those of the fp32 forward.
 """
 from __future__ import annotations
 
@@ -97,3 +105,146 @@ def input_gradients(model, mesh_graph, grad_output: torch.Tensor, scale_output: 
         lib.pdg_graph_colsum3(B, plan.ptr.data_ptr(), ig.mean_stress.data_ptr(), load.data_ptr(), s)
         return InputGradients(local_stress=y, mean_stress=ig.mean_stress, pos=ig.pos,
                               edge_attr=ig.edge_attr.view(edge_attr.shape), load=load)
+
+
+@dataclass
+class InputTangents:
+    """``local_stress`` (N, 3): the forward output of the same call.  ``d_local_stress`` (N, 3): the Jacobian of
+    ``local_stress`` with respect to (``mean_stress``, ``pos``, ``edge_attr``) applied to the given directions."""
+    local_stress: torch.Tensor
+    d_local_stress: torch.Tensor
+
+
+def _checked_forward(model, mesh_graph, scale_output: bool, scale_input: bool, what: str):
+    """The guard, the plan and a need_grad forward as ``input_gradients`` runs them (the guard and the status
+    word of a plan built here in one host read).  Returns (plan, engine, P, stats8, y, ctx); y and ctx are
+    None where the zero-stress guard fires."""
+    pos, ms, edge_attr = mesh_graph.pos, mesh_graph.mean_stress, mesh_graph.edge_attr
+    dev = pos.device
+    if dev.type != "cuda":
+        raise RuntimeError(f"{what} runs on the MI355X HIP path only; move the batch to a HIP device (the CPU "
+                           "restatement lives in oracle/ and is test-only)")
+    if model.input_nodes_features_size != 6 or model.input_edges_features_size != 1 \
+            or model.output_nodes_features_size != 3:
+        raise ValueError("HIP path supports the reference feature sizes (6 node, 1 edge, 3 outputs)")
+    s = stream_handle(dev)
+    flag = torch.zeros(2, dtype=torch.int32, device=dev)
+    plan = plan_for(mesh_graph, status=flag[1:])
+    msf = ms.detach().float().contiguous()
+    lib.pdg_any_nonzero(msf.data_ptr(), msf.numel(), flag.data_ptr(), s)
+    nonzero, status = flag.tolist()
+    if not plan._checked:
+        if plan.status.data_ptr() == flag[1:].data_ptr():
+            try:
+                plan.check_status(status)
+            except AssertionError:
+                mesh_graph.__dict__.pop("_plan_cache", None)
+                raise
+        else:
+            plan.validate()
+    eng = model._engine_for(dev)
+    P = {n: model.get_parameter(n).detach() for n in PARAM_NAMES}
+    stats8 = model.stats_tensor(dev)
+    if scale_output:
+        P["_std_local_stress"] = stats8[5:6]
+    if not nonzero:
+        return plan, eng, P, stats8, None, None
+    y, ctx = eng.forward(P, stats8, plan, pos.detach().float().contiguous(), msf,
+                         mesh_graph.nodes_types.reshape(-1).to(torch.int64).contiguous(),
+                         edge_attr.detach().reshape(-1).float().contiguous(), model.message_passing_steps,
+                         bool(scale_input), bool(scale_output), True)
+    return plan, eng, P, stats8, y, ctx
+
+
+def _direction(t, shape, name, dev):
+    if t is None:
+        return None
+    if t.device.type != "cuda":
+        raise RuntimeError(f"input_tangents runs on the MI355X HIP path only; move {name} to a HIP device")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have the shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _formatted_directions(plan, stats8, scale_input, d_ms, d_pos, d_ea, d_load):
+    """(dx_in (N, 6), de_in (E,) in plan order): the directions through pdg_format_inputs' linear map
+    (models.py:140-162: / std with scale_input; the node-type column has tangent 0)."""
+    N, E = plan.n_nodes, plan.n_edges
+    dev = stats8.device
+    dx_in = torch.zeros(N, 6, dtype=torch.float32, device=dev)
+    if d_load is not None:   # broadcast to the nodes of each graph: the adjoint of InputGradients.load
+        ptr = plan.ptr.long()
+        per_node = torch.repeat_interleave(d_load, ptr[1:] - ptr[:-1], dim=0, output_size=N)
+        d_ms = per_node if d_ms is None else d_ms + per_node
+    if d_ms is not None:
+        dx_in[:, 0:3] = d_ms / stats8[3] if scale_input else d_ms
+    if d_pos is not None:
+        dx_in[:, 3:5] = d_pos / stats8[1] if scale_input else d_pos
+    if d_ea is None:
+        de_in = torch.zeros(E, dtype=torch.float32, device=dev)
+    else:
+        de_in = d_ea.reshape(-1)[plan.perm.long()]
+        de_in = (de_in / stats8[7] if scale_input else de_in).contiguous()
+    return dx_in, de_in
+
+
+def input_tangents(model, mesh_graph, d_mean_stress=None, d_pos=None, d_edge_attr=None, d_load=None,
+                   scale_output: bool = True, scale_input: bool = True,
+                   chain_edge_lengths: bool = False) -> InputTangents:
+    """The Jacobian-vector product of ``model.forward(mesh_graph, scale_output, scale_input).local_stress`` with
+    the input directions ``d_mean_stress`` (N, 3), ``d_pos`` (N, 2), ``d_edge_attr`` (the shape of the batch's
+    ``edge_attr``, in its edge order) and ``d_load`` (B, 3), a change of each graph's imposed mean stress,
+    broadcast to its nodes and added to ``d_mean_stress`` (the adjoint of ``InputGradients.load``).  Missing
+    directions are zero; at least one must be given.  The model takes ``edge_attr`` as an independent input:
+    ``chain_edge_lengths=True`` adds the change of the edge lengths that follows ``d_pos`` (pdg_edge_len_tan;
+    periodic pairs and coincident nodes keep their constant length 0), so that ``d_pos`` is the total derivative
+    for a mesh whose lengths follow its nodes.  The linearisation is the fp32 forward's own: its stored relu
+    masks.  Works with or without ``torch.no_grad()``, never touches a parameter's ``.grad``, raises on CPU
+    tensors; where the forward's zero-stress guard fires the output and the tangent are zero."""
+    given = (d_mean_stress, d_pos, d_edge_attr, d_load)
+    if all(d is None for d in given):
+        raise ValueError("input_tangents needs at least one of d_mean_stress, d_pos, d_edge_attr, d_load")
+    if chain_edge_lengths and d_pos is None:
+        raise ValueError("chain_edge_lengths=True needs d_pos")
+    with torch.no_grad():
+        plan, eng, P, stats8, y, ctx = _checked_forward(model, mesh_graph, scale_output, scale_input,
+                                                        "input_tangents")
+        dev = stats8.device
+        N, E, B = plan.n_nodes, plan.n_edges, plan.n_graphs
+        edge_attr = mesh_graph.edge_attr
+        d_ms = _direction(d_mean_stress, (N, 3), "d_mean_stress", dev)
+        d_p = _direction(d_pos, (N, 2), "d_pos", dev)
+        d_ea = _direction(d_edge_attr, edge_attr.shape, "d_edge_attr", dev)
+        d_ld = _direction(d_load, (B, 3), "d_load", dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        if y is None:
+            return InputTangents(local_stress=torch.zeros(N, 3, **f32), d_local_stress=torch.zeros(N, 3, **f32))
+        if chain_edge_lengths and E:
+            ei = mesh_graph.edge_index.to(torch.int64).contiguous()
+            dlen = torch.empty(E, **f32)
+            lib.pdg_edge_len_tan(E, N, ei[0].data_ptr(), ei[1].data_ptr(),
+                                 mesh_graph.pos.detach().float().contiguous().data_ptr(), d_p.data_ptr(),
+                                 edge_attr.detach().reshape(-1).float().contiguous().data_ptr(), dlen.data_ptr(),
+                                 stream_handle(dev))
+            d_ea = dlen.view(edge_attr.shape) if d_ea is None else d_ea + dlen.view(edge_attr.shape)
+        dx_in, de_in = _formatted_directions(plan, stats8, scale_input, d_ms, d_p, d_ea, d_ld)
+        return InputTangents(local_stress=y, d_local_stress=eng.tangent(P, ctx, dx_in, de_in))
+
+
+def localisation_tensor(model, mesh_graph, scale_output: bool = True, scale_input: bool = True) -> torch.Tensor:
+    """The stress localisation tensor ``A[n, i, j] = d local_stress[n, i] / d Sigma_j`` (N, 3, 3), Sigma the
+    imposed mean stress of node n's graph: one forward and three tangent passes with ``d_load = e_j``; column j
+    is bitwise ``input_tangents(..., d_load=e_j).d_local_stress``.  Zeros where the zero-stress guard fires."""
+    with torch.no_grad():
+        plan, eng, P, stats8, y, ctx = _checked_forward(model, mesh_graph, scale_output, scale_input,
+                                                        "localisation_tensor")
+        N, E, B = plan.n_nodes, plan.n_edges, plan.n_graphs
+        A = torch.zeros(N, 3, 3, dtype=torch.float32, device=stats8.device)
+        if y is None:
+            return A
+        for j in range(3):
+            d_load = torch.zeros(B, 3, dtype=torch.float32, device=stats8.device)
+            d_load[:, j] = 1.0
+            dx_in, de_in = _formatted_directions(plan, stats8, scale_input, None, None, None, d_load)
+            A[:, :, j] = eng.tangent(P, ctx, dx_in, de_in)
+        return A

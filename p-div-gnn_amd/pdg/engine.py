@@ -567,6 +567,76 @@ class EPDEngine:
         self._bwd_wgrads(b)
         self._bwd_epilogue(b)
 
+    # ------------------------------------------------------------------ tangent
+    def tangent(self, P: dict, ctx: FwdCtx, dx_in: torch.Tensor, de_in: torch.Tensor) -> torch.Tensor:
+        """The Jacobian-vector product of the forward that produced ``ctx`` (``need_grad=True``) with respect
+        to its formatted inputs: ``dx_in`` (N, 6) the tangent of x_in, ``de_in`` (E,) that of e_in in plan
+        order; returns d local_stress (N, 3); with ``ctx.scale_output``, ``P["_std_local_stress"]`` as in
+        :meth:`backward`.  The forward linearised at the stored activations
+        (csrc/pdg_tangent.hip); ``ctx`` is only read, so several tangent passes may share one forward.
+        Rolling buffers only: nothing is kept per step.  The (T1, T2) pairs of every LayerNorm tangent go
+        from producer to consumer in ``max_blocks`` doubles x 2, reduced inside the consumer."""
+        if self.sync is not None:
+            raise ValueError("the tangent pass does not run in exact (sync) data-parallel mode")
+        if ctx.x_in is None:
+            raise ValueError("the tangent pass needs the context of a need_grad=True forward")
+        plan, S, st = ctx.plan, ctx.steps, ctx.stats
+        N, E = plan.n_nodes, plan.n_edges
+        if tuple(dx_in.shape) != (N, 6) or tuple(de_in.shape) != (E,):
+            raise ValueError(f"dx_in must be ({N}, 6) and de_in ({E},), got {tuple(dx_in.shape)} and "
+                             f"{tuple(de_in.shape)}")
+        for t in (dx_in, de_in):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("dx_in / de_in must be contiguous fp32 tensors on the engine's device")
+        s, nb = stream_handle(self.device), self._nslabs_e
+        f64 = dict(dtype=torch.float64, device=self.device)
+        # pairs: node LayerNorms, the message LayerNorm, and two for the edge LayerNorms (pdg_edge_tan reads
+        # the previous step's while its blocks write this step's)
+        pr_n, pr_m, pr_e0, pr_e1 = (torch.empty(2 * self.max_blocks, **f64) for _ in range(4))
+        da2n, dx_a, dx_b, dP, dQ = (self._empty(N, L) for _ in range(5))
+        W1e, W2e = P["processor.edge_net.0.weight"], P["processor.edge_net.2.weight"]
+        g_e, g_n = P["processor.edge_net.4.weight"], P["processor.node_net.4.weight"]
+        self._t("node_enc_tan", lib.pdg_node_enc_tan, N, _p(dx_in), _p(ctx.a1_ne), _p(P["node_encoder.0.weight"]),
+                _p(P["node_encoder.2.weight"]), _p(ctx.a2_ne), st[0], _p(da2n), _p(pr_n), nb, s)
+        if E:
+            da2e_a, da2e_b, de_a, de_b, da2m = (self._empty(E, L) for _ in range(5))
+            daggr = self._empty(N, L)
+            self._t("edge_enc_tan", lib.pdg_edge_enc_tan, E, _p(de_in), _p(ctx.e_in), _p(P["edge_encoder.0.weight"]),
+                    _p(P["edge_encoder.0.bias"]), _p(P["edge_encoder.2.weight"]), _p(ctx.a2_ee), st[1], _p(da2e_a),
+                    _p(pr_e0), nb, s)
+        else:   # as the forward: every message aggregate, and so its tangent, is zero
+            daggr = torch.zeros(N, L, dtype=torch.float32, device=self.device)
+        # the LayerNorm whose tangent, plus the residual's, is dx_t / de_t: (its input a2, its statistics, its weight)
+        ln_n = (ctx.a2_ne, st[0], P["node_encoder.4.weight"])
+        ln_e = (ctx.a2_ee, st[1], P["edge_encoder.4.weight"])
+        dx_prev = de_prev = None
+        for t in range(S):
+            d = ctx.per_step[t]
+            self._t("node_pre_tan", lib.pdg_node_pre_tan, N, _p(da2n), _p(ln_n[0]), ln_n[1], _p(pr_n), nb,
+                    _p(ln_n[2]), _p(dx_prev), _p(dx_a), _p(W1e), _p(dP), _p(dQ), nb, s)
+            if E:
+                eu = d["eu"]
+                self._t("edge_tan" if eu else "edge_tan_last", lib.pdg_edge_tan, E, N, _p(da2e_a), _p(ln_e[0]),
+                        ln_e[1], _p(pr_e0), nb, _p(ln_e[2]), _p(de_prev), _p(de_a), _p(plan.src), _p(plan.dst),
+                        _p(dP), _p(dQ), _p(W1e), _p(W2e), _p(d["a1m"]), _p(d["a2m"]), st[d["i_m"]],
+                        _p(d["a1e"]) if eu else None, _p(d["a2e"]) if eu else None, st[d["i_e"]] if eu else None,
+                        _p(da2m), _p(da2e_b) if eu else None, _p(pr_m), _p(pr_e1) if eu else None, int(eu), nb, s)
+                self._t("segment_sum_tan", lib.pdg_segment_sum_tan, N, E, _p(plan.rowptr_dst), _p(da2m), _p(d["a2m"]),
+                        st[d["i_m"]], _p(pr_m), nb, _p(g_e), _p(daggr), nb, s)
+                ln_e = (d["a2e"], st[d["i_e"]], g_e)
+                da2e_a, da2e_b, pr_e0, pr_e1 = da2e_b, da2e_a, pr_e1, pr_e0
+                de_prev, de_a, de_b = de_a, de_b, de_a
+            self._t("node_net_tan", lib.pdg_node_net_tan, N, _p(daggr), _p(dx_a), _p(P["processor.node_net.0.weight"]),
+                    _p(P["processor.node_net.2.weight"]), _p(d["a1n"]), _p(d["a2n"]), st[d["i_n"]], _p(da2n), _p(pr_n),
+                    nb, s)
+            ln_n = (d["a2n"], st[d["i_n"]], g_n)
+            dx_prev, dx_a, dx_b = dx_a, dx_b, dx_a
+        dy = self._empty(N, 3)
+        self._t("decoder_tan", lib.pdg_decoder_tan, N, _p(da2n), _p(ln_n[0]), ln_n[1], _p(pr_n), nb, _p(ln_n[2]),
+                _p(dx_prev), _p(P["node_decoder.0.weight"]), _p(ctx.a1d), _p(P["node_decoder.2.weight"]),
+                _p(P["_std_local_stress"]) if ctx.scale_output else None, int(ctx.scale_output), _p(dy), nb, s)
+        return dy
+
     def _bwd_begin(self, P, ctx: FwdCtx, G) -> _Bwd:
         """W^T copies, the fused edge backward's slabs, the LayerNorm accumulators and pair rows."""
         E, S = ctx.plan.n_edges, ctx.steps

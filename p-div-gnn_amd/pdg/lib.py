@@ -93,6 +93,14 @@ SIGNATURES: dict[str, list] = {
     "pdg_edge_enc_gin": [I, P, P, P, P, P, P, P, P, I, P, P, P, P, I, P, I, P],
     "pdg_node_enc_gin": [I, P, P, P, P, P, P, P, I, P, P, P, I, P, P, I, P],
     "pdg_graph_colsum3": [I, P, P, P, P],
+    "pdg_node_enc_tan": [I] + [P] * 8 + [I, P],
+    "pdg_edge_enc_tan": [I] + [P] * 9 + [I, P],
+    "pdg_node_pre_tan": [I, P, P, P, P, I] + [P] * 6 + [I, P],
+    "pdg_edge_tan": [I, I, P, P, P, P, I] + [P] * 19 + [I, I, P],
+    "pdg_segment_sum_tan": [I, I, P, P, P, P, P, I, P, P, I, P],
+    "pdg_node_net_tan": [I] + [P] * 9 + [I, P],
+    "pdg_decoder_tan": [I, P, P, P, P, I] + [P] * 6 + [I, P, I, P],
+    "pdg_edge_len_tan": [I, I, P, P, P, P, P, P, P],
     "pdg_enc_narrow_reduce": [P, I, P, P, P],
     "pdg_edge_bwd_w2": [I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, P, I, I, P],
     "pdg_edge_gout_wc": [I, P, P, P, P, P, P, I, P, P, P, P, P, I, I, P],
