@@ -550,13 +550,20 @@ int pdg_nmse_fwd_bwd(int n_graphs, const int* ptr, const float* gt, const float*
 
 /* Divergence penalty (gnn_train.py:60-92) with the operator in CSR over global rows and
  * graph-local columns (col < n_i: x-derivative, else y-derivative), ptr = node offsets:
- * div[v] = A_v . [[sxx;sxy],[sxy;syy]], rows with node_type +-1 zeroed, loss_g = mean_v |div|^2. */
+ * div[v] = A_v . [[sxx;sxy],[sxy;syy]], rows with node_type +-1 zeroed, loss_g = mean_v |div|^2
+ * (reduce_abs: mean_v |div|), summed over the two components.  The A arrays may hold entries with
+ * col >= 2 n_g: they are ignored (gnn_train.py:74 slices them off); columns are never negative.  A graph
+ * without nodes (ptr[g] == ptr[g+1]) gets loss[g] = NaN, as torch.mean of an empty tensor, and no row of
+ * div is touched for it; nothing past row ptr[n_graphs] of div is written. */
 int pdg_div_fwd(int n_graphs, const int* ptr, const int* a_rowptr, const int* a_col,
                 const float* a_val, const int64_t* node_types, const float* sigma, int reduce_abs,
                 float* div, float* loss, void* stream);
 /* g_sigma (+)= A^T-weighted grads: uses A^T in CSR (at_rowptr over global nodes, at_row = source
  * row v, at_comp = 0/1 (x/y column block), at_val).  d loss_g / d div = 2 div / n_g ("square")
- * or sign(div) / n_g ("abs"), times *scale. */
+ * or sign(div) / n_g ("abs", sign(0) = 0), times *scale.  Unlike the A arrays, the A^T arrays must not
+ * hold an entry with col >= 2 n_g (pdg_div_plan drops them): at_comp is all the kernel knows of the column.
+ * Every row m < n_nodes is written (a node without A^T entries gets 0, or keeps its value when
+ * accumulating); a graph without nodes owns no row and changes nothing. */
 int pdg_div_bwd(int n_graphs, const int* ptr, int n_nodes, const int* at_rowptr, const int* at_row,
                 const int* at_comp, const float* at_val, const float* div, const float* scale,
                 int reduce_abs, int accumulate, float* g_sigma, void* stream);
@@ -622,7 +629,9 @@ int pdg_transpose128_batch(int n, const float* const* in_ptrs, const int* lds, f
 int pdg_nonfinite2(const float* x, int64_t n, const float* zero_flag, int* flags, int parity, void* stream);
 /* The step's loss scalars (gnn_train.py:189-197) in one launch: out[0] = *zero_flag (1 when NULL),
  * out[1] = scale_nmse * sum_g loss_nmse[g], out[2] = scale_div * sum_g loss_div[g] (0 when loss_div is
- * NULL), out[3] = out[1] + out[2]; fp64 sums in graph order, rounded once. */
+ * NULL), out[3] = out[1] + out[2].  Each sum is formed in fp64 in a fixed order and rounded to fp32, then
+ * multiplied by its scale in fp32 (a second rounding), and out[3] is the fp32 sum of the two products:
+ * out[1] and out[2] are within 2 roundings of the exact scaled sums. */
 int pdg_loss_reduce(int n_graphs, const float* loss_nmse, const float* loss_div, float scale_nmse,
                     float scale_div, const float* zero_flag, float* out, void* stream);
 /* Adam as torch.optim.Adam (amsgrad=False, weight_decay=0) stepped by GradScaler.step

@@ -221,7 +221,9 @@ extern "C" int pdg_nmse_bwd(int n_graphs, const int* ptr, int n_nodes, const flo
 // div[v][0] = sum_j a_j * (col_j < n ? sxx : sxy)[off + col_j mod n]
 // div[v][1] = sum_j a_j * (col_j < n ? sxy : syy)[off + col_j mod n]
 // One block of 1024 threads per graph (4x the 256-thread form's node parallelism: each node walks its
-// CSR row of the divergence operator with dependent loads).
+// CSR row of the divergence operator with dependent loads).  Entries with col >= 2 n are skipped (the A arrays
+// may hold them; the A^T arrays of div_bwd_kernel must not: at_comp is all it sees of the column).  A graph
+// without nodes touches no row and gets loss = (float)(0.0 / 0) = NaN, torch.mean of an empty tensor.
 __global__ __launch_bounds__(1024) void div_fwd_kernel(const int* __restrict__ ptr, const int* __restrict__ arp,
                                                       const int* __restrict__ acol, const float* __restrict__ aval,
                                                       const int64_t* __restrict__ types,
@@ -400,7 +402,9 @@ extern "C" int pdg_nonfinite2(const float* x, int64_t n, const float* zero_flag,
 
 // The step's loss scalars (gnn_train.py:189-197) in one launch: out[0] = *zero_flag (or 1 when NULL),
 // out[1] = scale_nmse * sum_g loss_nmse[g], out[2] = scale_div * sum_g loss_div[g] (0 when NULL),
-// out[3] = out[1] + out[2].  Sums in fp64, graph order, rounded once.
+// out[3] = out[1] + out[2].  Each sum is formed in fp64 in a fixed order (thread g mod 256 takes graph g, then
+// the block reduction) and rounded to fp32; the scale is applied in fp32 (a second rounding) and out[3] is
+// the fp32 sum of the two products.
 __global__ void loss_reduce_kernel(int B, const float* __restrict__ ln, const float* __restrict__ ld, float sn,
                                    float sd, const float* __restrict__ nz, float* __restrict__ out) {
   __shared__ double red[2 * 16];

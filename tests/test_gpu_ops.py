@@ -1259,11 +1259,18 @@ def test_bwd_epilogue_matches_separate_launches(env):
     assert not torch.equal(a["W"][0], torch.full((L, L), 0.25, device="cuda"))   # something was added
 
 
-@pytest.mark.parametrize("sizes,accumulate", [((5041,) * 8, 0), ((17, 2, 3000, 250), 1), ((9000, 20000, 8192), 0)])
+@pytest.mark.parametrize("sizes,accumulate", [((5041,) * 8, 0), ((17, 2, 3000, 250), 1), ((9000, 20000, 8192), 0),
+                                              ((1025, 1, 4096, 4097, 2), 0), ((1025, 1, 4096, 4097, 2), 1)])
 def test_nmse_fwd_bwd_equals_fwd_then_bwd(env, sizes, accumulate):
     """pdg_nmse_fwd_bwd (per-graph NMSE and its gradient in one launch) is bitwise pdg_nmse_fwd + pdg_nmse_bwd:
     losses, denominators and the gradient (written or accumulated); ragged graphs, and graphs past the
-    8,192 nodes whose values the kernel keeps in registers (the rest re-read).  Losses against fp64."""
+    8,192 nodes whose values the kernel keeps in registers (the rest re-read).  Against fp64 (loss_ref.nmse_ref,
+    autograd of the oracle's loss): losses and denominators within 1e-5 relative, the gradient rows within relative
+    L2 TOL (accumulated: after removing the base).  A 1-node graph (den = 0, between graphs on both sides of the
+    1024-thread stride and of the 4,096 nodes of one cached iteration) gets the IEEE quotients torch gives in fp32 on
+    the same input, inf or NaN, and leaves the other graphs' values alone."""
+    from loss_ref import nmse_ref
+    from oracle import epd_oracle as O
     lib, sh, _ = env
     s = sh()
     B, N = len(sizes), sum(sizes)
@@ -1284,8 +1291,34 @@ def test_nmse_fwd_bwd_equals_fwd_then_bwd(env, sizes, accumulate):
     for b in range(B):
         lo, hi = int(ptr[b]), int(ptr[b + 1])
         t, p = gt64[lo:hi], pr64[lo:hi]
+        if hi - lo == 1:
+            continue    # den = 0: below
         ref = (((t - p) ** 2).sum(0) / ((t - t.mean(0)) ** 2).sum(0)).mean()
         assert abs(float(l1[b]) - float(ref)) <= 1e-5 * abs(float(ref)), (b, float(l1[b]), float(ref))
+    loss64, den64, grad64 = nmse_ref(ptr, gt, pred, float(scale))
+    ok = torch.tensor([n > 1 for n in sizes])
+    rows_ok = torch.repeat_interleave(ok, torch.tensor(sizes))
+    dc, gc, bc = d1.cpu(), g1.cpu(), base.cpu()
+    assert bool(((l1.cpu().double() - loss64).abs() <= 1e-5 * loss64)[ok].all())
+    assert bool(((dc.double() - den64).abs() <= 1e-5 * den64)[ok].all()), (dc, den64)
+    # written: g1 is the gradient.  Accumulated: g1 = fl(base + v) carries the final addition's rounding, at most
+    # 2^-24 |g1| per element whatever v is, so ||(g1 - base) - grad|| <= ||v - grad|| + 2^-24 ||g1||: the kernel's
+    # own v is held to TOL, the addition to the format's bound (base is O(1), v as small as 1e-5 of it)
+    gv = gc.double() - (bc.double() if accumulate else 0)
+    slack = 2.0 ** -24 * float(gc[rows_ok].double().norm()) if accumulate else 0.0
+    err = float((gv[rows_ok] - grad64[rows_ok]).norm())
+    assert err <= TOL * float(grad64[rows_ok].norm()) + slack, (err, float(grad64[rows_ok].norm()), slack)
+    for b in (i for i, n in enumerate(sizes) if n == 1):
+        lo = int(ptr[b])
+        t, q = gt[lo:lo + 1].cpu(), pred[lo:lo + 1].cpu()
+        want = O.normalized_mse_loss_single(t, q)                       # fp32 on the CPU: x / 0
+        den32 = (t - t.mean(0)).square().sum(0)
+        wg = scale.cpu() * ((-2.0 * (t - q)) / den32) / 3.0
+        wg = bc[lo:lo + 1] + wg if accumulate else wg
+        assert float(den32.abs().max()) == 0 and float(dc[b].abs().max()) == 0
+        assert not bool(torch.isfinite(want)) and not bool(torch.isfinite(wg).any())
+        for got, exp in ((l1[b].cpu().reshape(1), want.reshape(1)), (gc[lo], wg[0])):
+            assert torch.equal(got.isnan(), exp.isnan()) and torch.equal(got[~got.isnan()], exp[~exp.isnan()]), (got, exp)
 
 
 @pytest.mark.parametrize("E,nb", [(77, 37), (4099, 37), (30011, 256), (100000, 256)])
