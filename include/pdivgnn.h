@@ -607,6 +607,52 @@ int pdg_eval_div(int n_graphs, const int* ptr, const int* a_rowptr, const int* a
                  const int64_t* node_types, const float* sigma, float mean, float std, int reduce_abs,
                  double* table, float* norm, float* norm_std, void* stream);
 
+/* ---------------------------------------------------------------- stress criteria */
+/* Failure criteria of a plane-stress field, their per-graph aggregates and the aggregates' gradients, built
+ * like the evaluation metrics above: one workgroup per graph over the node segments ptr[0..B], fp64 arithmetic
+ * from the fp32 inputs in a fixed order, kernel launches only (no float atomics, no memset, nothing allocated:
+ * both calls can be captured), a graph's values bitwise the same alone and inside any batch.  sigma: (N, 3)
+ * fp32 in xx, yy, xy order, unstandardised.  Per node, with m = (sx + sy) / 2, d = (sx - sy) / 2,
+ * r = sqrt(d^2 + sxy^2), s1 = m + r, s2 = m - r:
+ *   criterion 0  von Mises  sqrt(0.5 ((sx - sy)^2 + sx^2 + sy^2 + 6 sxy^2)) (datasets.py:82 of the reference);
+ *                           gradient (2 sx - sy, 2 sy - sx, 6 sxy) / (2 vm), 0 where vm == 0;
+ *   criterion 1  Tresca     max(2 r, |s1|, |s2|) (the out-of-plane principal stress is 0), the branch chosen in
+ *                           that order, the first winning an exact tie; gradient of the chosen branch with
+ *                           dr = (d / (2 r), -d / (2 r), sxy / r) (0 where r == 0), ds1,2 = (1/2, 1/2, 0) +- dr
+ *                           and sign(0) = 0;
+ *   criterion 2  Rankine    max(s1, 0); gradient ds1 where s1 > 0, else 0.
+ * weights: (N) fp32 or NULL (1 everywhere).  A node takes part in its graph's aggregates if and only if its
+ * weight is > 0 (0, negative and NaN weights exclude it: the weights are also the mask); W is the sum of the
+ * participating weights.
+ *
+ * pdg_stress_criteria.  table: (B, 4) fp64 =
+ *   max     M, the largest criterion value c over the participating nodes,
+ *   mean    sum w c / W,
+ *   pnorm   M (sum w (c / M)^p / W)^(1/p), 0 where M == 0 (scaled by M: no overflow for any finite c),
+ *   ks      M + log(sum w exp(rho (c - M)) / W) / rho.
+ * argmax: (B) int32, the graph-local index of the first participating node with c == M.  fields: NULL or (N, 6)
+ * fp32, rounded once from fp64 = von Mises, s1, s2, r, the principal angle atan2(sxy, d) / 2, the chosen
+ * criterion; written for every node of a non-empty graph, participating or not (scalar stores: no alignment
+ * requirement).  A graph without nodes or without a participating node gets a NaN row and argmax -1 (no field
+ * row is touched for an empty graph); so does a graph with a NaN criterion at a participating node.
+ * n_graphs <= 0, a NULL ptr, sigma, table or argmax, a criterion outside 0..2, p < 1 or not finite and
+ * rho <= 0 or not finite are refused on the host before any launch. */
+int pdg_stress_criteria(int n_graphs, const int* ptr, const float* sigma, const float* weights, int criterion,
+                        double p, double rho, double* table, int* argmax, float* fields, void* stream);
+/* g_sigma (N, 3) fp32 = g_value[g] d J_g / d sigma(n), J the aggregate 0 max, 1 mean, 2 pnorm, 3 ks of the same
+ * criterion, weights, p and rho; table and argmax as pdg_stress_criteria wrote them; g_value (B) fp32 or NULL
+ * (ones).  d J / d c_n times the criterion's gradient above, with d J / d c_n =
+ *   max     1 at argmax, 0 elsewhere (a subgradient where the maximum is attained more than once),
+ *   mean    w / W,
+ *   pnorm   (w / W) (c / J)^(p - 1), 0 where J == 0,
+ *   ks      w exp(rho (c - M)) / sum w exp(rho (c - M)).
+ * W and the ks sum are formed again here with one block sum (the table keeps its four columns).  A node that
+ * takes no part gets an exact zero row, a graph whose argmax is -1 NaN rows at its participating nodes, an empty
+ * graph nothing.  The host checks of pdg_stress_criteria, and a NULL g_sigma and an aggregate outside 0..3. */
+int pdg_stress_criteria_bwd(int n_graphs, const int* ptr, const float* sigma, const float* weights, int criterion,
+                            int aggregate, double p, double rho, const double* table, const int* argmax,
+                            const float* g_value, float* g_sigma, void* stream);
+
 /* ---------------------------------------------------------------- utilities */
 /* out (cols x rows, contiguous) = in^T for a (rows x cols) row-major matrix with row stride ld. */
 int pdg_transpose(int rows, int cols, int ld, const float* in, float* out, void* stream);

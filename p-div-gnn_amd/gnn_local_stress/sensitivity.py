@@ -12,6 +12,12 @@ produces parameter gradients only); this module is the supported route:
 One forward and one backward of the engine (pdg.engine) with two more launches next to the encoders'
 backward (pdg_node_enc_gin, pdg_edge_enc_gin) and one per-graph reduction (pdg_graph_colsum3).
 
+The cotangent of a peak stress depends on the forward output of the same call, so a failure criterion's
+aggregate (gnn_local_stress.criteria) is differentiated in one call, with one forward:
+
+    c = criterion_gradients(model, batch, "von_mises", "pnorm", weights=w, p=8.0)
+    c.value, c.argmax, c.load, c.pos, c.grad_output
+
 The other direction, how the whole field moves when an input moves, is the Jacobian-vector product:
 
     t = input_tangents(model, batch, d_load=...)          # t.local_stress, t.d_local_stress
@@ -52,59 +58,145 @@ def input_gradients(model, mesh_graph, grad_output: torch.Tensor, scale_output: 
     (``nodes_types`` is an integer label and gets none).  Works with or without ``torch.no_grad()``, never
     touches a parameter's ``.grad``, and raises on CPU tensors like the rest of the HIP path.  Where the
     forward's zero-stress guard fires (models.py:294-299) the output and every gradient are zero."""
-    pos, ms, edge_attr = mesh_graph.pos, mesh_graph.mean_stress, mesh_graph.edge_attr
-    dev = pos.device
-    if dev.type != "cuda" or grad_output.device.type != "cuda":
+    if mesh_graph.pos.device.type != "cuda" or grad_output.device.type != "cuda":
         raise RuntimeError("input_gradients runs on the MI355X HIP path only; move the batch and grad_output to a "
                            "HIP device (the CPU restatement lives in oracle/ and is test-only)")
-    if model.input_nodes_features_size != 6 or model.input_edges_features_size != 1 \
-            or model.output_nodes_features_size != 3:
-        raise ValueError("HIP path supports the reference feature sizes (6 node, 1 edge, 3 outputs)")
+    _check_sizes(model)
+    ms = mesh_graph.mean_stress
     if tuple(grad_output.shape) != tuple(ms.shape):
         raise ValueError(f"grad_output must have the shape of local_stress {tuple(ms.shape)}, "
                          f"got {tuple(grad_output.shape)}")
     with torch.no_grad():
-        f32 = dict(dtype=torch.float32, device=dev)
-        s = stream_handle(dev)
-        # the guard and the status word of a plan built here in one host read, as in forward
-        flag = torch.zeros(2, dtype=torch.int32, device=dev)
-        plan = plan_for(mesh_graph, status=flag[1:])
-        msf = ms.detach().float().contiguous()
-        lib.pdg_any_nonzero(msf.data_ptr(), msf.numel(), flag.data_ptr(), s)
-        nonzero, status = flag.tolist()
-        if not plan._checked:
-            if plan.status.data_ptr() == flag[1:].data_ptr():
-                try:
-                    plan.check_status(status)
-                except AssertionError:
-                    mesh_graph.__dict__.pop("_plan_cache", None)
-                    raise
-            else:
-                plan.validate()
-        N, E, B = plan.n_nodes, plan.n_edges, plan.n_graphs
-        if not nonzero:
-            return InputGradients(local_stress=torch.zeros(N, 3, **f32), mean_stress=torch.zeros(N, 3, **f32),
-                                  pos=torch.zeros(N, 2, **f32), edge_attr=torch.zeros(edge_attr.shape, **f32),
-                                  load=torch.zeros(B, 3, **f32))
-        eng = model._engine_for(dev)
-        P = {n: model.get_parameter(n).detach() for n in PARAM_NAMES}
-        stats8 = model.stats_tensor(dev)
-        y, ctx = eng.forward(P, stats8, plan, pos.detach().float().contiguous(), msf,
-                             mesh_graph.nodes_types.reshape(-1).to(torch.int64).contiguous(),
-                             edge_attr.detach().reshape(-1).float().contiguous(), model.message_passing_steps,
-                             bool(scale_input), bool(scale_output), True)
-        if scale_output:
-            P["_std_local_stress"] = stats8[5:6]
-        # the engine's backward fuses the weight gradients into the input-gradient chain: they land in scratch
-        # accumulators that are dropped here, never in a parameter's .grad
-        G = {n: torch.zeros_like(p) for n, p in P.items() if n in PARAM_NAMES}
-        ig = InputGrads(mean_stress=torch.empty(N, 3, **f32), pos=torch.empty(N, 2, **f32),
-                        edge_attr=torch.empty(E, **f32), stats8=stats8, scale_input=bool(scale_input))
-        eng.backward(P, ctx, grad_output.detach().float().contiguous(), G, input_grads=ig)
-        load = torch.empty(B, 3, **f32)
-        lib.pdg_graph_colsum3(B, plan.ptr.data_ptr(), ig.mean_stress.data_ptr(), load.data_ptr(), s)
-        return InputGradients(local_stress=y, mean_stress=ig.mean_stress, pos=ig.pos,
-                              edge_attr=ig.edge_attr.view(edge_attr.shape), load=load)
+        fw = _vjp_forward(model, mesh_graph, scale_output, scale_input)
+        if fw.y is None:
+            return _zero_gradients(fw.plan, mesh_graph.edge_attr, ms.device)
+        return _vjp_backward(fw, mesh_graph.edge_attr, grad_output.detach().float().contiguous(), scale_input)
+
+
+def _check_sizes(model) -> None:
+    if model.input_nodes_features_size != 6 or model.input_edges_features_size != 1 \
+            or model.output_nodes_features_size != 3:
+        raise ValueError("HIP path supports the reference feature sizes (6 node, 1 edge, 3 outputs)")
+
+
+@dataclass
+class _Forward:
+    """What the backward part needs of the forward part; ``y`` and ``ctx`` are None where the zero-stress guard
+    fired."""
+    plan: object
+    eng: object
+    P: dict
+    stats8: torch.Tensor
+    y: torch.Tensor | None
+    ctx: object
+
+
+def _vjp_forward(model, mesh_graph, scale_output: bool, scale_input: bool) -> _Forward:
+    """The forward part of ``input_gradients``: the guard and the status word of a plan built here in one host
+    read (as in forward), then the engine's need_grad forward."""
+    pos, ms, edge_attr = mesh_graph.pos, mesh_graph.mean_stress, mesh_graph.edge_attr
+    dev = pos.device
+    s = stream_handle(dev)
+    flag = torch.zeros(2, dtype=torch.int32, device=dev)
+    plan = plan_for(mesh_graph, status=flag[1:])
+    msf = ms.detach().float().contiguous()
+    lib.pdg_any_nonzero(msf.data_ptr(), msf.numel(), flag.data_ptr(), s)
+    nonzero, status = flag.tolist()
+    if not plan._checked:
+        if plan.status.data_ptr() == flag[1:].data_ptr():
+            try:
+                plan.check_status(status)
+            except AssertionError:
+                mesh_graph.__dict__.pop("_plan_cache", None)
+                raise
+        else:
+            plan.validate()
+    if not nonzero:
+        return _Forward(plan, None, {}, None, None, None)
+    eng = model._engine_for(dev)
+    P = {n: model.get_parameter(n).detach() for n in PARAM_NAMES}
+    stats8 = model.stats_tensor(dev)
+    y, ctx = eng.forward(P, stats8, plan, pos.detach().float().contiguous(), msf,
+                         mesh_graph.nodes_types.reshape(-1).to(torch.int64).contiguous(),
+                         edge_attr.detach().reshape(-1).float().contiguous(), model.message_passing_steps,
+                         bool(scale_input), bool(scale_output), True)
+    if scale_output:
+        P["_std_local_stress"] = stats8[5:6]
+    return _Forward(plan, eng, P, stats8, y, ctx)
+
+
+def _zero_gradients(plan, edge_attr, dev) -> InputGradients:
+    f32 = dict(dtype=torch.float32, device=dev)
+    N, B = plan.n_nodes, plan.n_graphs
+    return InputGradients(local_stress=torch.zeros(N, 3, **f32), mean_stress=torch.zeros(N, 3, **f32),
+                          pos=torch.zeros(N, 2, **f32), edge_attr=torch.zeros(edge_attr.shape, **f32),
+                          load=torch.zeros(B, 3, **f32))
+
+
+def _vjp_backward(fw: _Forward, edge_attr, grad_output: torch.Tensor, scale_input: bool) -> InputGradients:
+    """The backward part of ``input_gradients``: the engine's backward with ``input_grads`` on the forward's
+    context, then the per-graph column sums (pdg_graph_colsum3)."""
+    plan, P, stats8 = fw.plan, fw.P, fw.stats8
+    dev = stats8.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    N, E, B = plan.n_nodes, plan.n_edges, plan.n_graphs
+    # the engine's backward fuses the weight gradients into the input-gradient chain: they land in scratch
+    # accumulators that are dropped here, never in a parameter's .grad
+    G = {n: torch.zeros_like(p) for n, p in P.items() if n in PARAM_NAMES}
+    ig = InputGrads(mean_stress=torch.empty(N, 3, **f32), pos=torch.empty(N, 2, **f32),
+                    edge_attr=torch.empty(E, **f32), stats8=stats8, scale_input=bool(scale_input))
+    fw.eng.backward(P, fw.ctx, grad_output, G, input_grads=ig)
+    load = torch.empty(B, 3, **f32)
+    lib.pdg_graph_colsum3(B, plan.ptr.data_ptr(), ig.mean_stress.data_ptr(), load.data_ptr(), stream_handle(dev))
+    return InputGradients(local_stress=fw.y, mean_stress=ig.mean_stress, pos=ig.pos,
+                          edge_attr=ig.edge_attr.view(edge_attr.shape), load=load)
+
+
+@dataclass
+class CriterionGradients(InputGradients):
+    """The fields of ``InputGradients`` for the cotangent ``grad_output`` (N, 3) = ``g_value[g]`` times the
+    gradient of graph g's aggregate with respect to ``local_stress``, and ``value`` (B,) fp64, that aggregate of
+    the chosen criterion over ``local_stress``, with ``argmax`` (B,) int64, the graph-local index of the first
+    node that attains the criterion's maximum (-1 for a NaN graph)."""
+    value: torch.Tensor = None
+    argmax: torch.Tensor = None
+    grad_output: torch.Tensor = None
+
+
+def criterion_gradients(model, mesh_graph, criterion: str = "von_mises", aggregate: str = "pnorm", weights=None,
+                        p: float = 8.0, rho: float | None = None, g_value=None, scale_output: bool = True,
+                        scale_input: bool = True) -> CriterionGradients:
+    """The sensitivity of a stress criterion's per-graph aggregate (``gnn_local_stress.criteria``: ``criterion``
+    one of von_mises / tresca / rankine, ``aggregate`` one of max / mean / pnorm / ks, ``weights`` the
+    participation weights, ``p``, ``rho``; ``aggregate='ks'`` needs ``rho``) with respect to ``mean_stress``,
+    ``pos``, ``edge_attr`` and each graph's ``load``, in one call: one engine forward, the two criterion launches
+    on its output (pdg_stress_criteria, pdg_stress_criteria_bwd), one engine backward with that cotangent and the
+    per-graph column sums.  ``g_value`` (B,) scales each graph's cotangent (None: ones), so the gradients are
+    those of sum_g g_value[g] J_g.  With ``scale_output=False`` the criterion is evaluated on the standardised
+    field (local_stress - mean) / std the model then returns, not on a stress.  Where the zero-stress guard fires
+    every gradient is zero and ``value`` / ``argmax`` are those of a zero field.  Works with or without
+    ``torch.no_grad()``, never touches a parameter's ``.grad``, raises on CPU tensors."""
+    from . import criteria as C
+    cid = C._id(criterion, C.CRITERIA, "criterion")
+    aid = C._aggregate_id(aggregate, rho)
+    p, rho = C._check_p_rho(p, rho)
+    dev = mesh_graph.pos.device
+    if dev.type != "cuda":
+        raise RuntimeError("criterion_gradients runs on the MI355X HIP path only; move the batch to a HIP device "
+                           "(the CPU restatement lives in oracle/ and is test-only)")
+    _check_sizes(model)
+    with torch.no_grad():
+        fw = _vjp_forward(model, mesh_graph, scale_output, scale_input)
+        plan = fw.plan
+        w = C._weights_of(weights, plan.n_nodes, dev)
+        if fw.y is None:
+            z = _zero_gradients(plan, mesh_graph.edge_attr, dev)
+            table, argmax, _ = C._forward(plan.ptr, z.local_stress, w, cid, p, rho, False)
+            return CriterionGradients(**vars(z), value=table[:, aid], argmax=argmax.long(),
+                                      grad_output=torch.zeros_like(z.local_stress))
+        table, argmax, gy = C._grad(plan.ptr, fw.y, w, cid, aid, p, rho, g_value)
+        g = _vjp_backward(fw, mesh_graph.edge_attr, gy, scale_input)
+        return CriterionGradients(**vars(g), value=table[:, aid], argmax=argmax.long(), grad_output=gy)
 
 
 @dataclass

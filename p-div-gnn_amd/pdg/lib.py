@@ -115,6 +115,8 @@ SIGNATURES: dict[str, list] = {
     "pdg_div_bwd": [I, P, I, P, P, P, P, P, P, I, I, P, P],
     "pdg_eval_nmse": [I, P, P, P, P, P, P, P, P],
     "pdg_eval_div": [I, P, P, P, P, P, P, c_float, c_float, I, P, P, P, P],
+    "pdg_stress_criteria": [I, P, P, P, I, c_double, c_double, P, P, P, P],
+    "pdg_stress_criteria_bwd": [I, P, P, P, I, I, c_double, c_double, P, P, P, P, P],
     "pdg_transpose": [I, I, I, P, P, P],
     "pdg_nonfinite2": [P, c_int64, P, P, I, P],
     "pdg_loss_reduce": [I, P, P, c_float, c_float, P, P, P],
