@@ -653,6 +653,34 @@ int pdg_stress_criteria_bwd(int n_graphs, const int* ptr, const float* sigma, co
                             int aggregate, double p, double rho, const double* table, const int* argmax,
                             const float* g_value, float* g_sigma, void* stream);
 
+/* ---------------------------------------------------------------- homogenisation */
+/* Per-graph weighted integrals of a nodal field and the shift that makes its average equal a target
+ * (pdg_homog.hip), built like the stress criteria above: segmented by ptr[0..B], fp64 arithmetic from the fp32
+ * inputs in a fixed order, kernel launches only (no float atomics, no memset, nothing allocated: both calls can
+ * be captured).  With the nodal areas of pdg_nodal_areas as weights, S / (cell area) is the reference's
+ * mean_stress (integrate_field(sigma) / bounding_box.volume, scripts/generate_dataset.py:278-289) and S / W its
+ * mean_stress_material (integrate_field(sigma) / integrate_field(1)).
+ *
+ * pdg_graph_wmean.  rows: (N, n_cols) fp32, 1 <= n_cols <= 9; weights: (N) fp32 or NULL (ones).  A row takes
+ * part if and only if its weight is > 0 (the criteria's rule: 0, negative and NaN weights exclude it).  table:
+ * (B, n_cols + 1) fp64 = W_g = sum w, then S_g,c = sum w rows[., c] over the participating rows.  One 1024-thread
+ * workgroup per graph, thread t owning rows t, t + 1024, ... in that order and the block folded in a fixed
+ * order: a graph gets bitwise the same row alone and inside any batch, and from call to call.  A graph without
+ * rows or without a participating row gets zeros (its averages are then 0 / 0).  n_graphs <= 0, n_cols outside
+ * 1..9 and a NULL ptr, rows or table are refused on the host before any launch. */
+int pdg_graph_wmean(int n_graphs, const int* ptr, const float* rows, int n_cols, const float* weights,
+                    double* table, void* stream);
+/* out (N, 3) fp32 = sigma + shift_g with shift_g,c = (target[g, c] D_g - S_g,c) / W_g formed in fp64 and the sum
+ * rounded once; table as pdg_graph_wmean wrote it for sigma with n_cols = 3; target: (B, 3) fp32; denom: (B)
+ * fp64 = D_g, or NULL for D_g = W_g.  A constant shift c moves S / D by c W / D, so denom = the cell's area
+ * makes the average over the cell (the mean_stress convention) equal the target and denom = NULL the average
+ * over the material (mean_stress_material).  Every row of the graph is shifted, participating or not.  A graph
+ * whose W is not > 0 gets a NaN shift, hence NaN rows: a plain result would hide that it has no average.  out
+ * may alias sigma: an output element depends on its own input and its graph's table row only.  n_graphs <= 0
+ * (or >= 2^27) and a NULL ptr, sigma, table, target or out are refused on the host before any launch. */
+int pdg_mean_correct(int n_graphs, const int* ptr, const float* sigma, const double* table, const float* target,
+                     const double* denom, float* out, void* stream);
+
 /* ---------------------------------------------------------------- utilities */
 /* out (cols x rows, contiguous) = in^T for a (rows x cols) row-major matrix with row stride ld. */
 int pdg_transpose(int rows, int cols, int ld, const float* in, float* out, void* stream);
@@ -772,8 +800,21 @@ int pdg_div_plan(int n_nodes, int n_graphs, const int* ptr, long nnz, const int6
  * duplicates summed, structural zeros kept (every key the host keeps); *nnz (device int) entries of
  * the `capacity` >= 18 n_faces provided.  Sums are fp64 in face-index order, rounded once to fp32.
  * *status (device int) bits: 1 a face has det == 0 (its contributions are skipped; the host function
- * divides by zero there), 2 a face index is out of range (the face is ignored). */
+ * divides by zero there), 2 a face index is out of range (the face is ignored).
+ *
+ * pdg_nodal_areas: the lumped nodal areas area[n] = sum over the faces f that hold n of area_f / 3, with
+ * area_f = |det| / 2 and the det above, of pdg/meshgen.py nodal_areas.  For P1 triangles these are the
+ * reference's quadrature weights gathered to the nodes, so area / cell area is its op_mean_stress
+ * (scripts/generate_dataset.py:73-82).  The 3 n_faces (node, face) items are grouped by node and ordered by
+ * face; a node's thread sums its terms in that order in fp64 and rounds once to fp32 (no float atomics: the
+ * result does not depend on the order of the slot atomics).  A face that names a node twice gives it two
+ * terms, a face of zero area contributes 0 and is no error, a node of no face gets exactly 0.  bbox: 4 fp32 =
+ * (xmin, xmax, ymin, ymax) of all points, whether a face uses them or not.  *status (device int) bit 1: a
+ * face index is out of range (the face is ignored, the index never dereferenced).  Scratch and host checks
+ * as pdg_node_labels. */
 long pdg_mesh_fields_scratch_bytes(int n_nodes, int n_faces);
+int pdg_nodal_areas(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces, float* area,
+                    float* bbox, int* status, void* scratch, long scratch_bytes, void* stream);
 int pdg_node_labels(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
                     int64_t* labels, int* info, void* scratch, long scratch_bytes, void* stream);
 int pdg_p1_div_operator(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,

@@ -5,8 +5,10 @@
 //                        -1 on an internal boundary (a hole's rim), 0 elsewhere
 //   pdg_p1_div_operator  the area-averaged P1 nodal divergence operator A = [Dx | Dy] (N x 2N) of
 //                        pdg/meshgen.py p1_divergence_operator, as COO sorted by (row, col)
+//   pdg_nodal_areas      the lumped nodal areas sum area_f / 3 of pdg/meshgen.py nodal_areas (the reference's
+//                        quadrature weights gathered to the nodes, generate_dataset.py:73-82) and the bounding box
 //
-// Both are the grouping of pdg_group.hpp (histogram, exclusive scan, atomic fill of 64-bit slots,
+// All are the grouping of pdg_group.hpp (histogram, exclusive scan, atomic fill of 64-bit slots,
 // bounded per-row sort) followed by one thread per row walking its sorted slots.
 //
 // Labels.  The 3 F undirected edges are grouped by their smaller endpoint and ordered by the larger
@@ -24,6 +26,9 @@
 // (column node, face), so the faces that contribute to one entry are neighbours, in face order.
 // Each row's thread sums the entry in fp64 in that order and rounds once to fp32.  The fp64
 // expressions are meshgen's, evaluated without contraction.
+//
+// Areas.  The 3 F (node, face) items are grouped by node and ordered by face; each node's thread sums
+// area_f / 3 in fp64 in that order and rounds once to fp32.  A face of zero area adds 0 and is no error here.
 //
 // A face with an index outside [0, n_nodes) sets a status bit and is ignored: validity is decided
 // once per face (fok[]) before anything indexes with its entries.  Every loop is bounded by a row
@@ -47,6 +52,7 @@ constexpr int CT = 1024;   // threads of the component search's single workgroup
 
 enum { ST_RANGE = 1, ST_NONMANIFOLD = 2, ST_CAP = 4 };   // info[2] of pdg_node_labels
 enum { DV_DEGENERATE = 1, DV_RANGE = 2 };                // *status of pdg_p1_div_operator
+enum { AR_RANGE = 1 };                                   // *status of pdg_nodal_areas
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -384,6 +390,68 @@ __global__ __launch_bounds__(PT) void div_emit_kernel(int n, const float* __rest
   }
 }
 
+// ------------------------------------------------------------------------------ nodal areas
+__global__ __launch_bounds__(PT) void area_face_kernel(int nf, const int64_t* __restrict__ faces, int n,
+                                                       int* __restrict__ fok, int* __restrict__ cnt,
+                                                       int* __restrict__ status) {
+  int bad = 0;
+  for (long f = (long)blockIdx.x * PT + threadIdx.x; f < nf; f += (long)gridDim.x * PT) {
+    const int64_t* t = faces + 3 * f;
+    const int ok = in_range(t, n);
+    fok[f] = ok;
+    if (ok)
+      for (int v = 0; v < 3; ++v) atomicAdd(&cnt[(int)t[v]], 1);
+    else
+      bad = 1;
+  }
+  if (bad) atomicOr(status, AR_RANGE);
+}
+
+// Item i = 3 f + v: face f under its vertex faces[f][v], ordered by face (then by v: a face that names a node
+// twice gives it two terms, as the host's add.at over faces.ravel() does).
+struct FaceByNode {
+  const int64_t* faces;
+  const int* fok;
+  u64* sorted;
+  __device__ bool item(long i, int& major, unsigned& minor) const {
+    const long f = i / 3;
+    if (!fok[f]) return false;
+    major = (int)faces[i];
+    minor = (unsigned)f;
+    return true;
+  }
+  __device__ void emit(long k, int, u64 slot) const { sorted[k] = slot; }
+};
+
+// Row r: the sum of its faces' area / 3 in fp64, in face order, rounded once; a node of no face gets exactly 0.
+// Block 0 also writes the bounding box as (xmin, xmax, ymin, ymax).
+__global__ __launch_bounds__(PT) void area_emit_kernel(int n, const float* __restrict__ p, int dim,
+                                                       const int64_t* __restrict__ faces,
+                                                       const int* __restrict__ rowptr, const u64* __restrict__ sorted,
+                                                       const float* __restrict__ part, int nparts,
+                                                       float* __restrict__ area, float* __restrict__ bbox) {
+#pragma clang fp contract(off)
+  __shared__ float bb[4];
+  if (blockIdx.x == 0) {   // uniform over the block: bbox_load's barrier is reached by all of it or none
+    bbox_load(part, nparts, bb);
+    if (threadIdx.x == 0) {
+      bbox[0] = bb[0];
+      bbox[1] = bb[2];
+      bbox[2] = bb[1];
+      bbox[3] = bb[3];
+    }
+  }
+  for (int r = blockIdx.x * PT + threadIdx.x; r < n; r += gridDim.x * PT) {
+    const int b = rowptr[r], e = rowptr[r + 1];
+    double a = 0.0;
+    for (int k = b; k < e; ++k) {
+      const unsigned f = (unsigned)(sorted[k] >> 32);
+      a += 0.5 * fabs(triangle(p, dim, faces + 3 * (size_t)f).det) / 3.0;
+    }
+    area[r] = (float)a;
+  }
+}
+
 }  // namespace
 
 extern "C" long pdg_mesh_fields_scratch_bytes(int n_nodes, int n_faces) {
@@ -459,5 +527,35 @@ extern "C" int pdg_p1_div_operator(int n_nodes, const float* points, int dim, in
   hipLaunchKernelGGL(div_emit_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt, s.sorted,
                      ucnt, rows, cols, vals, nnz);
   PDG_CHECK_LAUNCH("pdg_p1_div_operator");
+  return PDG_OK;
+}
+
+extern "C" int pdg_nodal_areas(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                               float* area, float* bbox, int* status, void* scratch, long scratch_bytes,
+                               void* stream) {
+  PDG_CHECK_ARG(sizes_ok(n_nodes, n_faces) && (dim == 2 || dim == 3),
+                "pdg_nodal_areas: bad sizes (n_nodes > 0, n_faces >= 0, dim 2 or 3, n_nodes + 1024 and "
+                "9 n_faces + 1024 < 2^31)");
+  PDG_CHECK_ARG(points && area && bbox && status && scratch && (faces || n_faces == 0),
+                "pdg_nodal_areas: null argument");
+  PDG_CHECK_ARG(scratch_bytes >= pdg_mesh_fields_scratch_bytes(n_nodes, n_faces),
+                "pdg_nodal_areas: scratch too small");
+  hipStream_t st = (hipStream_t)stream;
+  LabelScratch s;   // the labels' layout holds all that is needed here: bbox, cnt | fill, bsum, fok, 3 F slots twice
+  label_layout(n_nodes, n_faces, &s, (char*)scratch);
+  const long n = n_nodes;
+  int* cnt = s.zero;             // [n + 1]
+  int* fill = cnt + n + 1;       // [n]
+  const int nbb = bbox_blocks(n_nodes);
+  hipLaunchKernelGGL(bbox_kernel, dim3(nbb), dim3(BBOX_T), 0, st, n_nodes, points, dim, s.bbox, s.ctr);
+  hipLaunchKernelGGL(clear_kernel, dim3(grid_for(2 * n + 1)), dim3(PT), 0, st, s.zero, 2 * n + 1, (int*)nullptr, 0L,
+                     (int*)nullptr, 0L, status);
+  if (n_faces > 0)
+    hipLaunchKernelGGL(area_face_kernel, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok, cnt,
+                       status);
+  group(FaceByNode{faces, s.fok, s.sorted}, 3L * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
+  hipLaunchKernelGGL(area_emit_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt, s.sorted,
+                     s.bbox, nbb, area, bbox);
+  PDG_CHECK_LAUNCH("pdg_nodal_areas");
   return PDG_OK;
 }

@@ -59,7 +59,7 @@ def predict_and_save(model: models.EncodeProcessDecode, dataloader: DataLoader, 
 
 @torch.no_grad()
 def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic: bool = True,
-                 divergence: bool = False):
+                 divergence: bool = False, enforce_mean: str | None = None):
     """The reference's published workload (``scripts/benchmark_gnn_fem.py:388-415`` then one
     forward) from a bare mesh: ``mesh`` is a legacy-VTK path or a ``(points, faces)`` pair of
     arrays / tensors, ``mean_stress`` the imposed mean field (3 values).  The graph, the node
@@ -67,9 +67,15 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     needed.  Returns the graph ``Data`` with ``local_stress`` (the prediction) and
     ``nodes_types``; with ``divergence`` returns ``(data, div)``, ``div`` the prediction's
     divergence penalty (``losses.compute_divergence`` with the mesh's P1 operator, which is
-    kept as ``data.op_div_matrix``).  Triangle meshes only."""
+    kept as ``data.op_div_matrix``).  ``enforce_mean`` = ``"cell"`` or ``"material"`` builds the nodal
+    areas with the graph (``data.node_area``, ``data.cell_area``) and returns the prediction shifted so
+    that its volume average in that convention equals ``mean_stress``
+    (``gnn_local_stress.homogenise.enforce_mean``); None returns the model's output as it is.  Triangle
+    meshes only."""
     from pdg.devgraph import convert_mesh_to_graph
-    from . import losses, vtk_io
+    from . import homogenise, losses, vtk_io
+    if enforce_mean is not None:
+        homogenise._id(enforce_mean, homogenise.CONVENTIONS, "convention")
     if isinstance(mesh, (str, Path)):
         points, faces = vtk_io.read_legacy_vtk(mesh)
     else:
@@ -80,8 +86,11 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     if faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError(f"predict_mesh takes triangle meshes only (faces of shape (F, 3)), got "
                          f"{tuple(faces.shape)}: quad meshes are not built on the device")
-    data = convert_mesh_to_graph(points, faces, mean_stress, None, periodic, divergence)
+    data = convert_mesh_to_graph(points, faces, mean_stress, None, periodic, divergence,
+                                 areas=enforce_mean is not None)
     data.local_stress = model.forward(data, scale_output=True, scale_input=True).local_stress
+    if enforce_mean is not None:
+        data.local_stress = homogenise.enforce_mean(data.local_stress, data, convention=enforce_mean)
     if not divergence:
         return data
     div = losses.compute_divergence(data.local_stress, data.op_div_matrix, data.surfaces_nodes_for_div)

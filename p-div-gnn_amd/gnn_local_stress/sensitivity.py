@@ -22,6 +22,7 @@ The other direction, how the whole field moves when an input moves, is the Jacob
 
     t = input_tangents(model, batch, d_load=...)          # t.local_stress, t.d_local_stress
     A = localisation_tensor(model, batch)                 # A[n, i, j] = d sigma_i(n) / d Sigma_j
+    M = mean_localisation(model, batch)                   # (B, 3, 3): the volume average of A, I when consistent
 
 One forward and one tangent pass per direction (pdg.engine.EPDEngine.tangent, csrc/pdg_tangent.hip): the
 forward linearised at its own stored activations, so the relu masks are those of the fp32 forward.
@@ -340,3 +341,18 @@ def localisation_tensor(model, mesh_graph, scale_output: bool = True, scale_inpu
             dx_in, de_in = _formatted_directions(plan, stats8, scale_input, None, None, None, d_load)
             A[:, :, j] = eng.tangent(P, ctx, dx_in, de_in)
         return A
+
+
+def mean_localisation(model, mesh_graph, weights=None, cell_area=None, convention: str = "cell",
+                      scale_output: bool = True, scale_input: bool = True) -> torch.Tensor:
+    """(B, 3, 3) fp64: the volume average of ``localisation_tensor`` per graph, d <sigma>_i / d Sigma_j, its nine
+    columns averaged in one ``pdg_graph_wmean`` call (``gnn_local_stress.homogenise.graph_average``;
+    ``weights``, ``cell_area`` and ``convention`` as there, the batch's ``node_area`` / ``cell_area`` by
+    default).  The identity for a mean-consistent model.  The graph LayerNorm's statistics run over the whole
+    batch and couple its graphs, so for a batch this is the response to moving every graph's load at once."""
+    from . import homogenise as H
+    # refused before the forward and the three tangent passes
+    cellwise = H._convention(convention, cell_area if cell_area is not None else H._of_batch(mesh_graph, "cell_area"))
+    A = localisation_tensor(model, mesh_graph, scale_output, scale_input)
+    avg = H.graph_average(A.reshape(A.shape[0], 9), mesh_graph, weights, cell_area)
+    return (avg.mean_cell if cellwise else avg.mean_material).reshape(-1, 3, 3)

@@ -11,6 +11,8 @@ host restatement's ``edge_index`` and ``edge_attr`` (``tests/test_gpu_devgraph.p
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from .graph import Data
@@ -122,14 +124,45 @@ def p1_divergence(points: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     return torch.sparse_coo_tensor(idx[:, :nnz], vals[:nnz], (n, 2 * n), is_coalesced=True)
 
 
+class NodalAreas(NamedTuple):
+    """``area`` (N,) float32: the lumped nodal areas; ``cell_area`` (1,) float64: the bounding box's area,
+    (xmax - xmin)(ymax - ymin) formed in fp64 from the float32 extremes.  Both on the device."""
+    area: torch.Tensor
+    cell_area: torch.Tensor
+
+
+def nodal_areas(points: torch.Tensor, faces: torch.Tensor) -> NodalAreas:
+    """The quadrature weights of the reference's volume averages on the device (``pdg_nodal_areas``,
+    csrc/pdg_meshfields.hip): ``area[n]`` is the sum of area / 3 over the triangles that hold node n, to one
+    float32 ulp of ``pdg.meshgen.nodal_areas`` (the same fp64 terms in the same order), and ``area / cell_area``
+    is the reference's ``op_mean_stress`` (``scripts/generate_dataset.py:73-82``).  A node of no face gets 0, a
+    face of zero area adds 0.  One host read (the status word).  Raises ValueError for a face index outside the
+    mesh.  Triangle meshes only."""
+    pts, fcs, scratch, nbytes = _mesh_tensors(points, faces, "nodal_areas")
+    n, dim = pts.shape
+    nf = fcs.shape[0]
+    dev = pts.device
+    area = torch.empty(n, dtype=torch.float32, device=dev)
+    bbox = torch.empty(4, dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    lib.pdg_nodal_areas(n, pts.data_ptr(), dim, nf, fcs.data_ptr() if nf else None, area.data_ptr(),
+                        bbox.data_ptr(), status.data_ptr(), scratch.data_ptr(), nbytes, stream_handle(dev))
+    if int(status.item()) & 1:
+        raise ValueError(f"faces hold a node index outside [0, {n})")
+    b = bbox.double()
+    return NodalAreas(area, ((b[1] - b[0]) * (b[3] - b[2])).reshape(1))
+
+
 def convert_mesh_to_graph(points: torch.Tensor, faces: torch.Tensor, mean_stress,
                           node_labels: torch.Tensor | None = None, periodic: bool = True,
-                          divergence: bool = False) -> Data:
+                          divergence: bool = False, areas: bool = False) -> Data:
     """``benchmark_gnn_fem.py:388-415`` on the device: the graph of one FEM sample, ready for
     ``EncodeProcessDecode`` (pos reduced to (x, y) float32, mean stress broadcast to every
     node, node labels as both ``surfaces_nodes_for_div`` and ``nodes_types``).  Without
     ``node_labels`` they are computed from the mesh on the device (``node_labels`` above,
-    strict); ``divergence`` also sets ``op_div_matrix`` (``p1_divergence``)."""
+    strict); ``divergence`` also sets ``op_div_matrix`` (``p1_divergence``); ``areas`` also sets
+    ``node_area`` (N,) and ``cell_area`` (1,) (``nodal_areas``), the weights and the cell of the volume
+    averages of ``gnn_local_stress.homogenise``."""
     edge_index, edge_attr = mesh_graph(points, faces, periodic)
     n = points.shape[0]
     dev = points.device
@@ -142,4 +175,6 @@ def convert_mesh_to_graph(points: torch.Tensor, faces: torch.Tensor, mean_stress
                surfaces_nodes_for_div=labels, nodes_types=labels.clone(), is_periodic=periodic)
     if divergence:
         out.op_div_matrix = p1_divergence(points, faces)
+    if areas:
+        out.node_area, out.cell_area = nodal_areas(points, faces)
     return out

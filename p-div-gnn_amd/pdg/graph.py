@@ -22,8 +22,9 @@ import torch
 
 from . import meshgen
 
-_NODE_KEYS = ("pos", "mean_stress", "local_stress", "nodes_types", "surfaces_nodes_for_div", "x")
+_NODE_KEYS = ("pos", "mean_stress", "local_stress", "nodes_types", "surfaces_nodes_for_div", "x", "node_area")
 _EDGE_KEYS = ("edge_attr",)
+_GRAPH_KEYS = ("cell_area",)   # one entry per graph: (1,) in a Data, (B,) in a Batch
 
 
 class Data:
@@ -117,7 +118,7 @@ class Batch(Data):
         ecounts = [d.num_edges for d in data_list]
         ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         eptr = np.concatenate([[0], np.cumsum(ecounts)]).astype(np.int64)
-        for k in _NODE_KEYS + _EDGE_KEYS:
+        for k in _NODE_KEYS + _EDGE_KEYS + _GRAPH_KEYS:
             vals = [d.__dict__.get(k) for d in data_list]
             if all(v is not None for v in vals):
                 setattr(b, k, torch.cat(vals, 0))
@@ -166,6 +167,10 @@ class Batch(Data):
             v = self.__dict__.get(k)
             if v is not None:
                 setattr(out, k, v[e0:e1])
+        for k in _GRAPH_KEYS:
+            v = self.__dict__.get(k)
+            if v is not None:
+                setattr(out, k, v[idx:idx + 1])
         out.edge_index = self.edge_index[:, e0:e1] - n0
         op = self._data_list[idx].__dict__.get("op_div_matrix")
         if op is not None:

@@ -128,6 +128,9 @@ SIGNATURES: dict[str, list] = {
     "pdg_mesh_fields_scratch_bytes": [I, I],
     "pdg_node_labels": [I, P, I, I, P, P, P, P, ctypes.c_long, P],
     "pdg_p1_div_operator": [I, P, I, I, P, P, P, P, ctypes.c_long, P, P, P, ctypes.c_long, P],
+    "pdg_nodal_areas": [I, P, I, I, P, P, P, P, P, ctypes.c_long, P],
+    "pdg_graph_wmean": [I, P, P, I, P, P, P],
+    "pdg_mean_correct": [I, P, P, P, P, P, P, P],
 }
 # the entry points that return a value, not a status: called as they are (no error check, not counted in
 # lib.calls, not passed to lib.hook)

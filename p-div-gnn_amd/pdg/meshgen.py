@@ -171,6 +171,29 @@ def p1_divergence_operator(pos: np.ndarray, faces: np.ndarray):
     return (uniq // (2 * n)).astype(np.int64), (uniq % (2 * n)).astype(np.int64), acc.astype(np.float32)
 
 
+def nodal_areas(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Lumped nodal areas of a triangle mesh: (area (N,) float32, bbox (4,) float32 = xmin, xmax, ymin, ymax).
+    ``area[n]`` is the sum of ``area_f / 3`` over the faces that hold n: for P1 triangles exactly the reference's
+    quadrature weights gathered to the nodes, so ``area / cell area`` is its ``op_mean_stress``
+    (``scripts/generate_dataset.py:73-82``) and ``sum(area * field)`` its ``integrate_field``.  fp64 from the
+    float32 coordinates with the ``det`` of ``p1_divergence_operator``, a node's terms added in face order and
+    rounded once; a node of no face gets 0.  The host restatement of ``pdg_nodal_areas``
+    (csrc/pdg_meshfields.hip)."""
+    p32 = np.asarray(pos, dtype=np.float32)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    p = p32.astype(np.float64)
+    a, b, c = faces[:, 0], faces[:, 1], faces[:, 2]
+    xa, ya = p[a, 0], p[a, 1]
+    xb, yb = p[b, 0], p[b, 1]
+    xc, yc = p[c, 0], p[c, 1]
+    det = (xb - xa) * (yc - ya) - (xc - xa) * (yb - ya)  # 2 * signed area
+    third = 0.5 * np.abs(det) / 3.0
+    acc = np.zeros(len(p))
+    np.add.at(acc, faces.ravel(), np.repeat(third, 3))
+    bbox = np.array([p32[:, 0].min(), p32[:, 0].max(), p32[:, 1].min(), p32[:, 1].max()], np.float32)
+    return acc.astype(np.float32), bbox
+
+
 def node_labels(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, int, int]:
     """``compute_node_labels`` (``datasets.py:122-179``) from the mesh alone: (labels (N,) int64,
     boundary components, external ones).  A boundary edge belongs to exactly one face; the
