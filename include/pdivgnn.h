@@ -820,6 +820,77 @@ int pdg_node_labels(int n_nodes, const float* points, int dim, int n_faces, cons
 int pdg_p1_div_operator(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
                         int64_t* rows, int64_t* cols, float* vals, long capacity, int* nnz, int* status,
                         void* scratch, long scratch_bytes, void* stream);
+/* pdg_boundary_vectors: the lumped outward boundary vectors of pdg/meshgen.py boundary_vectors.  A boundary edge
+ * is pdg_node_labels' (an undirected edge of exactly one face; the same device code finds them).  For the boundary
+ * edge (a, b) of face (a, b, c), in the face's own vertex order, r = (yb - ya, -(xb - xa)) is formed in fp64 from
+ * the fp32 coordinates and negated if r . (pc - pa) > 0: it then points out of the material, away from the third
+ * vertex, whatever the face's orientation, and r = length * n_outward.  bvec (n_nodes, 2) fp32: bvec[n] = 1/2 sum
+ * r_e, and blen (n_nodes) fp32: blen[n] = 1/2 sum |r_e|, over the boundary edges that hold n, each summed in fp64
+ * in ascending order of the edge's other endpoint and rounded once (a manifold boundary node has two edges; no
+ * float atomics: the result does not depend on the order of the slot atomics).  A node that is not on a boundary
+ * edge gets exact zeros.  sigma(n) . bvec[n], that is fx = sxx mx + sxy my and fy = sxy mx + syy my, is the
+ * nodal boundary force, the lumped traction integral.  *status (device int) bits:
+ *   1  a face index is out of range: the face is ignored, the index never dereferenced;
+ *   2  a boundary node has other than two boundary edges (outputs still written);
+ *   4  a boundary edge belongs to a face of zero area (det == 0 with the det above): it adds its length to blen
+ *      and nothing to bvec.
+ * scratch holds pdg_boundary_vectors_scratch_bytes(n_nodes, n_faces) bytes, a size of its own (the endpoints of
+ * up to 3 n_faces boundary edges are grouped a second time; pdg_mesh_fields_scratch_bytes is unchanged; < 0 under
+ * the same conditions).  Sizes, null pointers and the scratch size are checked on the host before any HIP call;
+ * kernel launches only, so the call can be captured. */
+long pdg_boundary_vectors_scratch_bytes(int n_nodes, int n_faces);
+int pdg_boundary_vectors(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces, float* bvec,
+                         float* blen, int* status, void* scratch, long scratch_bytes, void* stream);
+
+/* ---------------------------------------------------------------- boundary residuals */
+/* What a plane-stress field does on the boundary of the periodic cell (pdg_boundary.hip), built like the
+ * homogenisation above: segmented by ptr[0..B], fp64 arithmetic from the fp32 inputs in a fixed order, kernel
+ * launches only (no atomics, no memset, nothing allocated: both calls can be captured).
+ *
+ * pdg_boundary_residuals.  sigma: (N, 3) fp32 in xx, yy, xy order; bvec (N, 2) and blen (N) as
+ * pdg_boundary_vectors wrote them; labels: (N) int64, the +1 / -1 / 0 of nodes_types; rowptr_dst (N + 1 int32),
+ * src (int32, dst-sorted) and perm (int32) of the graph plan (pdg_graph_plan) and edge_attr (fp32, original edge
+ * order): the four edge arguments may all be NULL, the periodic columns are then 0.  With f(n) = sigma(n) .
+ * bvec[n], a node takes part in the traction sums if and only if its label is +1 or -1 and blen[n] > 0 (the
+ * criteria's rule: a zero, negative or NaN blen excludes it).  A periodic connection is an incoming edge of n (the
+ * plan's dst-sorted lists) whose edge_attr is exactly 0; one whose source lies outside n's graph is not read.
+ * table: (B, 9) fp64 =
+ *   0     L_int = sum blen over the participating nodes labelled -1,
+ *   1     L_ext = sum blen over the participating nodes labelled +1,
+ *   2     T2 = sum over -1 of |f|^2 / blen, the integral of the squared traction over the hole's edge,
+ *   3, 4  F_int = sum over -1 of f, the net force on the hole (0 for a traction-free hole),
+ *   5, 6  F_ext = sum over +1 of f, the net force on the cell (0 for any periodic field in equilibrium),
+ *   7     P2 = 1/2 sum_n sum over the periodic edges into n of |sigma(n) - sigma(src)|^2 (the plain sum of the
+ *         three components),
+ *   8     n_pairs = 1/2 the number of those edges.
+ * argmax: (B) int32, the graph-local index of the first participating -1 node that attains the largest
+ * |f| / blen; -1 when there is none, and -1 when a participating node of the graph has a NaN traction (a plain
+ * maximum would hide the NaN, as in pdg_stress_criteria).  One 1024-thread workgroup per graph, thread t owning
+ * rows t, t + 1024, ... in that order and the block folded in a fixed order: a graph gets bitwise the same row and
+ * argmax alone and inside any batch, and from call to call.  A graph without rows gets zeros and argmax -1.
+ * n_graphs <= 0, a NULL ptr, sigma, bvec, blen, labels, table or argmax, and partial edge arguments are refused
+ * on the host before any launch.
+ *
+ * pdg_boundary_residuals_bwd.  out (N, 3) fp32 = the gradient with respect to sigma of
+ *   sum_g g_traction[g] T2_g / L_int,g + g_periodic[g] P2_g / n_pairs,g,
+ * the mean-square hole traction and the mean-square periodic jump; table as the forward wrote it; g_traction,
+ * g_periodic: (B) fp64, either may be NULL (taken as 0).  Per row: at a participating -1 node
+ * (2 / blen) (fx [mx, 0, my] + fy [0, my, mx]) times g_traction / L_int; at any node 2 sum over the periodic
+ * edges into n of (sigma(n) - sigma(src)) times g_periodic / n_pairs.  Precondition: the periodic term is the
+ * full gradient when the periodic connections appear in both directions, as compute_periodic_graph and
+ * pdg_mesh_graph build them and coalesce keeps them.  Node-parallel and without atomics: a row depends on its own
+ * inputs, its neighbours' sigma and its graph's table row.  Rows that take no part get exact zeros (a zero weight
+ * switches its term off); a graph whose denominator is not > 0 under a non-zero weight gets NaN in that term's
+ * participating rows (the NaN rule of the criteria and of pdg_mean_correct).  Each output is formed in fp64 and
+ * rounded once.  n_graphs <= 0 (or >= 2^27), a NULL ptr, sigma, bvec, blen, labels, table or out, and partial
+ * edge arguments are refused on the host before any launch. */
+int pdg_boundary_residuals(int n_graphs, const int* ptr, const float* sigma, const float* bvec, const float* blen,
+                           const int64_t* labels, const int* rowptr_dst, const int* src, const int* perm,
+                           const float* edge_attr, double* table, int* argmax, void* stream);
+int pdg_boundary_residuals_bwd(int n_graphs, const int* ptr, const float* sigma, const float* bvec,
+                               const float* blen, const int64_t* labels, const int* rowptr_dst, const int* src,
+                               const int* perm, const float* edge_attr, const double* table,
+                               const double* g_traction, const double* g_periodic, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,9 @@
 //                        pdg/meshgen.py p1_divergence_operator, as COO sorted by (row, col)
 //   pdg_nodal_areas      the lumped nodal areas sum area_f / 3 of pdg/meshgen.py nodal_areas (the reference's
 //                        quadrature weights gathered to the nodes, generate_dataset.py:73-82) and the bounding box
+//   pdg_boundary_vectors the lumped outward boundary vectors bvec[n] = 1/2 sum length * n_outward and lengths
+//                        blen[n] = 1/2 sum length over the boundary edges at n, of pdg/meshgen.py boundary_vectors:
+//                        sigma(n) . bvec[n] is the nodal boundary force (the lumped traction integral)
 //
 // All are the grouping of pdg_group.hpp (histogram, exclusive scan, atomic fill of 64-bit slots,
 // bounded per-row sort) followed by one thread per row walking its sorted slots.
@@ -29,6 +32,10 @@
 //
 // Areas.  The 3 F (node, face) items are grouped by node and ordered by face; each node's thread sums
 // area_f / 3 in fp64 in that order and rounds once to fp32.  A face of zero area adds 0 and is no error here.
+//
+// Boundary vectors.  The labels' boundary-edge pass (the same device code) marks the boundary edges among the
+// sorted slots; their 2 endpoint items are grouped by node and ordered by the other endpoint, and each node's
+// thread sums its edges' r = length * n_outward and |r| in fp64 in that order and rounds once to fp32.
 //
 // A face with an index outside [0, n_nodes) sets a status bit and is ignored: validity is decided
 // once per face (fok[]) before anything indexes with its entries.  Every loop is bounded by a row
@@ -53,6 +60,7 @@ constexpr int CT = 1024;   // threads of the component search's single workgroup
 enum { ST_RANGE = 1, ST_NONMANIFOLD = 2, ST_CAP = 4 };   // info[2] of pdg_node_labels
 enum { DV_DEGENERATE = 1, DV_RANGE = 2 };                // *status of pdg_p1_div_operator
 enum { AR_RANGE = 1 };                                   // *status of pdg_nodal_areas
+enum { BV_RANGE = 1, BV_NONMANIFOLD = 2, BV_FLAT = 4 };  // *status of pdg_boundary_vectors
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -77,6 +85,16 @@ struct DivScratch {
   u64* sorted;   // [9F]
 };
 
+struct BvecScratch {
+  int* zero;     // cleared block: cnt [n + 1] | fill [n] | cnt2 [n + 1] | fill2 [n]
+  int* bsum;
+  int* fok;      // [F]
+  int* brow;     // [3F] the row (smaller endpoint) of sorted slot k when it is a boundary edge, else -1
+  u64* slots;    // [6F] (the edges' grouping uses the first 3F)
+  u64* sorted;   // [3F] the edges by smaller endpoint
+  u64* sorted2;  // [6F] the boundary edges' endpoints by node
+};
+
 size_t label_layout(int n, int nf, LabelScratch* s, char* base) {
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -96,6 +114,26 @@ size_t label_layout(int n, int nf, LabelScratch* s, char* base) {
   t.be_v = (int*)take(sizeof(int) * e);
   t.slots = (u64*)take(sizeof(u64) * e);
   t.sorted = (u64*)take(sizeof(u64) * e);
+  if (s) *s = t;
+  return o;
+}
+
+size_t bvec_layout(int n, int nf, BvecScratch* s, char* base) {
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + o : nullptr;
+    o += align_up(bytes);
+    return p;
+  };
+  const size_t e = 3 * (size_t)std::max(nf, 1);
+  BvecScratch t;
+  t.zero = (int*)take(sizeof(int) * (4 * (size_t)n + 2));
+  t.bsum = (int*)take(sizeof(int) * scan_bsum_len(n));
+  t.fok = (int*)take(sizeof(int) * (size_t)std::max(nf, 1));
+  t.brow = (int*)take(sizeof(int) * e);
+  t.slots = (u64*)take(sizeof(u64) * 2 * e);
+  t.sorted = (u64*)take(sizeof(u64) * e);
+  t.sorted2 = (u64*)take(sizeof(u64) * 2 * e);
   if (s) *s = t;
   return o;
 }
@@ -131,7 +169,7 @@ __device__ __forceinline__ bool in_range(const int64_t* __restrict__ t, int n) {
 // ----------------------------------------------------------------------------------- labels
 __global__ __launch_bounds__(PT) void label_face_kernel(int nf, const int64_t* __restrict__ faces, int n,
                                                         int* __restrict__ fok, int* __restrict__ cnt,
-                                                        int* __restrict__ info) {
+                                                        int* __restrict__ status) {
   int bad = 0;
   for (long f = (long)blockIdx.x * PT + threadIdx.x; f < nf; f += (long)gridDim.x * PT) {
     const int64_t* t = faces + 3 * f;
@@ -146,7 +184,7 @@ __global__ __launch_bounds__(PT) void label_face_kernel(int nf, const int64_t* _
       bad = 1;
     }
   }
-  if (bad) atomicOr(&info[2], ST_RANGE);
+  if (bad) atomicOr(status, ST_RANGE);   // ST_RANGE == BV_RANGE
 }
 
 // Undirected edge j of face f (j = i % 3: (0,1), (1,2), (2,0)) under its smaller endpoint.
@@ -166,7 +204,27 @@ struct EdgeByMin {
   __device__ void emit(long k, int, u64 slot) const { sorted[k] = slot; }
 };
 
-// Row r's boundary edges: the larger endpoints that occur exactly once among its sorted slots.
+// Row r's boundary edges: the larger endpoints that occur exactly once among its sorted slots.  fn(k, v, c): sorted
+// slot k is the row's c-th boundary edge (r, v).  Returns their number.  The one definition of a boundary edge on the
+// device, shared by the labels and the boundary vectors.
+template <class F>
+__device__ __forceinline__ int for_boundary_edges(int r, const int* __restrict__ rowptr,
+                                                  const u64* __restrict__ sorted, F fn) {
+  const int b = rowptr[r], e = rowptr[r + 1];
+  int c = 0;
+  for (int k = b; k < e;) {
+    const int v = (int)(sorted[k] >> 32);
+    int len = 1;
+    while (k + len < e && (int)(sorted[k + len] >> 32) == v) ++len;
+    if (len == 1) {
+      fn(k, v, c);
+      ++c;
+    }
+    k += len;
+  }
+  return c;
+}
+
 // write == 0: count them into bcnt[r], add them to both endpoints' boundary degree, start r's
 // label at r.  write != 0: store them at bptr[r] (the scanned counts).
 __global__ __launch_bounds__(PT) void boundary_kernel(int n, const int* __restrict__ rowptr,
@@ -175,24 +233,15 @@ __global__ __launch_bounds__(PT) void boundary_kernel(int n, const int* __restri
                                                       int* __restrict__ lab, const int* __restrict__ bptr,
                                                       int* __restrict__ be_u, int* __restrict__ be_v) {
   for (int r = blockIdx.x * PT + threadIdx.x; r < n; r += gridDim.x * PT) {
-    const int b = rowptr[r], e = rowptr[r + 1];
-    int c = 0;
-    for (int k = b; k < e;) {
-      const int v = (int)(sorted[k] >> 32);
-      int len = 1;
-      while (k + len < e && (int)(sorted[k + len] >> 32) == v) ++len;
-      if (len == 1) {
-        if (write) {
-          be_u[bptr[r] + c] = r;
-          be_v[bptr[r] + c] = v;
-        } else {
-          atomicAdd(&bdeg[r], 1);
-          atomicAdd(&bdeg[v], 1);
-        }
-        ++c;
+    const int c = for_boundary_edges(r, rowptr, sorted, [&](int, int v, int j) {
+      if (write) {
+        be_u[bptr[r] + j] = r;
+        be_v[bptr[r] + j] = v;
+      } else {
+        atomicAdd(&bdeg[r], 1);
+        atomicAdd(&bdeg[v], 1);
       }
-      k += len;
-    }
+    });
     if (!write) {
       bcnt[r] = c;
       lab[r] = r;
@@ -452,6 +501,85 @@ __global__ __launch_bounds__(PT) void area_emit_kernel(int n, const float* __res
   }
 }
 
+// ------------------------------------------------------------------------- boundary vectors
+// brow[k] = r where sorted slot k is a boundary edge of row r, -1 elsewhere (every k < rowptr[n] lies in one row);
+// cnt2: the boundary edges at each node, both endpoints counted.
+__global__ __launch_bounds__(PT) void bvec_mark_kernel(int n, const int* __restrict__ rowptr,
+                                                       const u64* __restrict__ sorted, int* __restrict__ brow,
+                                                       int* __restrict__ cnt2) {
+  for (int r = blockIdx.x * PT + threadIdx.x; r < n; r += gridDim.x * PT) {
+    for (int k = rowptr[r]; k < rowptr[r + 1]; ++k) brow[k] = -1;
+    for_boundary_edges(r, rowptr, sorted, [&](int k, int v, int) {
+      brow[k] = r;
+      atomicAdd(&cnt2[r], 1);
+      atomicAdd(&cnt2[v], 1);
+    });
+  }
+}
+
+// Item i = 2 k + side: boundary edge k (a sorted slot of the edges' grouping) under its smaller (side 0) or larger
+// (side 1) endpoint, ordered by the other endpoint.
+struct EndByNode {
+  const int* rowptr;   // of the edges' grouping: rowptr[n] slots are in use
+  int n;
+  const int* brow;
+  const u64* sorted;
+  u64* sorted2;
+  __device__ bool item(long i, int& major, unsigned& minor) const {
+    const long k = i >> 1;
+    if (k >= rowptr[n] || brow[k] < 0) return false;
+    const int u = brow[k], v = (int)(sorted[k] >> 32);
+    major = (i & 1) ? v : u;
+    minor = (unsigned)((i & 1) ? u : v);
+    return true;
+  }
+  __device__ void emit(long k, int, u64 slot) const { sorted2[k] = slot; }
+};
+
+// Node r: its boundary edges in ascending order of the other endpoint.  Edge (a, b) of face (a, b, c), in the
+// face's own order: r = (yb - ya, -(xb - xa)), negated when r . (pc - pa) > 0 so that it points away from c;
+// bvec = 1/2 sum r, blen = 1/2 sum |r|, fp64 sums rounded once.  A node of no boundary edge gets exact zeros.
+__global__ __launch_bounds__(PT) void bvec_emit_kernel(int n, const float* __restrict__ p, int dim,
+                                                       const int64_t* __restrict__ faces,
+                                                       const int* __restrict__ rowptr2,
+                                                       const u64* __restrict__ sorted2,
+                                                       const u64* __restrict__ sorted, float* __restrict__ bvec,
+                                                       float* __restrict__ blen, int* __restrict__ status) {
+#pragma clang fp contract(off)
+  int bad = 0;
+  for (int r = blockIdx.x * PT + threadIdx.x; r < n; r += gridDim.x * PT) {
+    const int b = rowptr2[r], e = rowptr2[r + 1];
+    double sx = 0.0, sy = 0.0, sl = 0.0;
+    if (e > b && e - b != 2) bad |= BV_NONMANIFOLD;
+    for (int q = b; q < e; ++q) {
+      const unsigned k = (unsigned)(sorted2[q] & 0xffffffffu) >> 1;
+      const unsigned pos = (unsigned)(sorted[k] & 0xffffffffu);
+      const unsigned f = pos / 3, j = pos - 3 * f;
+      const int64_t* t = faces + 3 * (size_t)f;
+      const size_t ia = (size_t)t[j], ib = (size_t)t[j == 2 ? 0 : j + 1], ic = (size_t)t[j == 0 ? 2 : j - 1];
+      const double xa = p[ia * dim], ya = p[ia * dim + 1];
+      const double xb = p[ib * dim], yb = p[ib * dim + 1];
+      const double xc = p[ic * dim], yc = p[ic * dim + 1];
+      double rx = yb - ya, ry = -(xb - xa);
+      sl += sqrt(rx * rx + ry * ry);
+      if (triangle(p, dim, t).det == 0.0) {
+        bad |= BV_FLAT;
+        continue;
+      }
+      if (rx * (xc - xa) + ry * (yc - ya) > 0.0) {
+        rx = -rx;
+        ry = -ry;
+      }
+      sx += rx;
+      sy += ry;
+    }
+    bvec[2 * (size_t)r] = (float)(0.5 * sx);
+    bvec[2 * (size_t)r + 1] = (float)(0.5 * sy);
+    blen[r] = (float)(0.5 * sl);
+  }
+  if (bad) atomicOr(status, bad);
+}
+
 }  // namespace
 
 extern "C" long pdg_mesh_fields_scratch_bytes(int n_nodes, int n_faces) {
@@ -483,7 +611,7 @@ extern "C" int pdg_node_labels(int n_nodes, const float* points, int dim, int n_
                      (int*)nullptr, 0L, (int*)nullptr);
   if (n_faces > 0)
     hipLaunchKernelGGL(label_face_kernel, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok, cnt,
-                       info);
+                       info + 2);
   group(EdgeByMin{faces, s.fok, s.sorted}, 3L * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
   hipLaunchKernelGGL(boundary_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, cnt, s.sorted, 0, bdeg, bcnt, s.lab,
                      (const int*)nullptr, (int*)nullptr, (int*)nullptr);
@@ -557,5 +685,42 @@ extern "C" int pdg_nodal_areas(int n_nodes, const float* points, int dim, int n_
   hipLaunchKernelGGL(area_emit_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt, s.sorted,
                      s.bbox, nbb, area, bbox);
   PDG_CHECK_LAUNCH("pdg_nodal_areas");
+  return PDG_OK;
+}
+
+extern "C" long pdg_boundary_vectors_scratch_bytes(int n_nodes, int n_faces) {
+  if (!sizes_ok(n_nodes, n_faces)) return -1;
+  return (long)bvec_layout(n_nodes, n_faces, nullptr, nullptr);
+}
+
+extern "C" int pdg_boundary_vectors(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                                    float* bvec, float* blen, int* status, void* scratch, long scratch_bytes,
+                                    void* stream) {
+  PDG_CHECK_ARG(sizes_ok(n_nodes, n_faces) && (dim == 2 || dim == 3),
+                "pdg_boundary_vectors: bad sizes (n_nodes > 0, n_faces >= 0, dim 2 or 3, n_nodes + 1024 and "
+                "9 n_faces + 1024 < 2^31)");
+  PDG_CHECK_ARG(points && bvec && blen && status && scratch && (faces || n_faces == 0),
+                "pdg_boundary_vectors: null argument");
+  PDG_CHECK_ARG(scratch_bytes >= pdg_boundary_vectors_scratch_bytes(n_nodes, n_faces),
+                "pdg_boundary_vectors: scratch too small");
+  hipStream_t st = (hipStream_t)stream;
+  BvecScratch s;
+  bvec_layout(n_nodes, n_faces, &s, (char*)scratch);
+  const long n = n_nodes;
+  int* cnt = s.zero;             // [n + 1]
+  int* fill = cnt + n + 1;       // [n]
+  int* cnt2 = fill + n;          // [n + 1]
+  int* fill2 = cnt2 + n + 1;     // [n]
+  hipLaunchKernelGGL(clear_kernel, dim3(grid_for(4 * n + 2)), dim3(PT), 0, st, s.zero, 4 * n + 2, (int*)nullptr, 0L,
+                     (int*)nullptr, 0L, status);
+  if (n_faces > 0)
+    hipLaunchKernelGGL(label_face_kernel, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok, cnt,
+                       status);
+  group(EdgeByMin{faces, s.fok, s.sorted}, 3L * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
+  hipLaunchKernelGGL(bvec_mark_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, cnt, s.sorted, s.brow, cnt2);
+  group(EndByNode{cnt, n_nodes, s.brow, s.sorted, s.sorted2}, 6L * n_faces, n_nodes, cnt2, fill2, s.bsum, s.slots, st);
+  hipLaunchKernelGGL(bvec_emit_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt2, s.sorted2,
+                     s.sorted, bvec, blen, status);
+  PDG_CHECK_LAUNCH("pdg_boundary_vectors");
   return PDG_OK;
 }

@@ -59,7 +59,7 @@ def predict_and_save(model: models.EncodeProcessDecode, dataloader: DataLoader, 
 
 @torch.no_grad()
 def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic: bool = True,
-                 divergence: bool = False, enforce_mean: str | None = None):
+                 divergence: bool = False, enforce_mean: str | None = None, boundary: bool = False):
     """The reference's published workload (``scripts/benchmark_gnn_fem.py:388-415`` then one
     forward) from a bare mesh: ``mesh`` is a legacy-VTK path or a ``(points, faces)`` pair of
     arrays / tensors, ``mean_stress`` the imposed mean field (3 values).  The graph, the node
@@ -70,10 +70,13 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     kept as ``data.op_div_matrix``).  ``enforce_mean`` = ``"cell"`` or ``"material"`` builds the nodal
     areas with the graph (``data.node_area``, ``data.cell_area``) and returns the prediction shifted so
     that its volume average in that convention equals ``mean_stress``
-    (``gnn_local_stress.homogenise.enforce_mean``); None returns the model's output as it is.  Triangle
-    meshes only."""
+    (``gnn_local_stress.homogenise.enforce_mean``); None returns the model's output as it is.
+    ``boundary`` builds the boundary vectors with the graph (``data.boundary_vec``, ``data.boundary_len``)
+    and also returns the boundary residuals of the returned prediction
+    (``gnn_local_stress.boundary.boundary_residuals``; the periodic columns with ``periodic``), as the last
+    value: ``(data, res)`` or ``(data, div, res)``.  Triangle meshes only."""
     from pdg.devgraph import convert_mesh_to_graph
-    from . import homogenise, losses, vtk_io
+    from . import boundary as bd, homogenise, losses, vtk_io
     if enforce_mean is not None:
         homogenise._id(enforce_mean, homogenise.CONVENTIONS, "convention")
     if isinstance(mesh, (str, Path)):
@@ -87,14 +90,15 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
         raise ValueError(f"predict_mesh takes triangle meshes only (faces of shape (F, 3)), got "
                          f"{tuple(faces.shape)}: quad meshes are not built on the device")
     data = convert_mesh_to_graph(points, faces, mean_stress, None, periodic, divergence,
-                                 areas=enforce_mean is not None)
+                                 areas=enforce_mean is not None, boundary=bool(boundary))
     data.local_stress = model.forward(data, scale_output=True, scale_input=True).local_stress
     if enforce_mean is not None:
         data.local_stress = homogenise.enforce_mean(data.local_stress, data, convention=enforce_mean)
+    res = bd.boundary_residuals(data.local_stress, data, periodic=bool(periodic)) if boundary else None
     if not divergence:
-        return data
+        return (data, res) if boundary else data
     div = losses.compute_divergence(data.local_stress, data.op_div_matrix, data.surfaces_nodes_for_div)
-    return data, div
+    return (data, div, res) if boundary else (data, div)
 
 
 @torch.no_grad()

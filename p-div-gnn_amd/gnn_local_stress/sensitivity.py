@@ -18,6 +18,12 @@ aggregate (gnn_local_stress.criteria) is differentiated in one call, with one fo
     c = criterion_gradients(model, batch, "von_mises", "pnorm", weights=w, p=8.0)
     c.value, c.argmax, c.load, c.pos, c.grad_output
 
+The boundary residuals (gnn_local_stress.boundary: the mean-square traction on the hole's edge and the mean-square
+jump across the periodic connections) are differentiated the same way:
+
+    s = boundary_gradients(model, batch, traction=1.0, periodic=0.0)
+    s.value, s.load, s.pos, s.grad_output
+
 The other direction, how the whole field moves when an input moves, is the Jacobian-vector product:
 
     t = input_tangents(model, batch, d_load=...)          # t.local_stress, t.d_local_stress
@@ -198,6 +204,55 @@ def criterion_gradients(model, mesh_graph, criterion: str = "von_mises", aggrega
         table, argmax, gy = C._grad(plan.ptr, fw.y, w, cid, aid, p, rho, g_value)
         g = _vjp_backward(fw, mesh_graph.edge_attr, gy, scale_input)
         return CriterionGradients(**vars(g), value=table[:, aid], argmax=argmax.long(), grad_output=gy)
+
+
+@dataclass
+class BoundaryGradients(InputGradients):
+    """The fields of ``InputGradients`` for the cotangent ``grad_output`` (N, 3) = the gradient of sum_g
+    traction[g] T2_g / L_int,g + periodic[g] P2_g / n_pairs,g with respect to ``local_stress``, and ``value`` (B,)
+    fp64, graph g's term of that sum (NaN where a denominator is 0)."""
+    value: torch.Tensor = None
+    grad_output: torch.Tensor = None
+
+
+def boundary_gradients(model, mesh_graph, traction=1.0, periodic=0.0, scale_output: bool = True,
+                       scale_input: bool = True) -> BoundaryGradients:
+    """The sensitivity of the boundary residuals of the prediction (``gnn_local_stress.boundary``: ``traction``
+    times the mean-square traction on the hole's edge T2 / L_int plus ``periodic`` times the mean-square jump across
+    the periodic connections P2 / n_pairs; the weights are scalars or (B,) tensors) with respect to
+    ``mean_stress``, ``pos``, ``edge_attr`` and each graph's ``load``, in one call: one engine forward, the two
+    boundary launches on its output (pdg_boundary_residuals, pdg_boundary_residuals_bwd), one engine backward with
+    that cotangent and the per-graph column sums.  The batch carries ``boundary_vec`` / ``boundary_len``
+    (``convert_mesh_to_graph(..., boundary=True)``).  ``pos`` here goes through the node features only: the
+    dependence of the boundary vectors on the coordinates is not chained (nor, as in ``input_gradients``, that of
+    ``edge_attr``).  With ``scale_output=False`` the residuals are those of the standardised field the model then
+    returns, not of a stress.  Where the zero-stress guard fires every gradient is zero and ``value`` is that of a
+    zero field.  Works with or without ``torch.no_grad()``, never touches a parameter's ``.grad``, raises on CPU
+    tensors."""
+    from . import boundary as Bd
+    dev = mesh_graph.pos.device
+    if dev.type != "cuda":
+        raise RuntimeError("boundary_gradients runs on the MI355X HIP path only; move the batch to a HIP device "
+                           "(the CPU restatement is test-only, tests/boundary_ref.py)")
+    _check_sizes(model)
+    with torch.no_grad():
+        fw = _vjp_forward(model, mesh_graph, scale_output, scale_input)
+        B = fw.plan.n_graphs
+        gt, gp = Bd._weight(traction, B, dev, "traction"), Bd._weight(periodic, B, dev, "periodic")
+
+        def value(table):
+            # a term whose weight is 0 is switched off, as in the backward launch: 0 * (0 / 0) stays out
+            zero = torch.zeros(B, dtype=torch.float64, device=dev)
+            return (torch.where(gt == 0, zero, gt * table[:, 2] / table[:, 0])
+                    + torch.where(gp == 0, zero, gp * table[:, 7] / table[:, 8]))
+
+        if fw.y is None:
+            z = _zero_gradients(fw.plan, mesh_graph.edge_attr, dev)
+            table, _ = Bd._forward(Bd._setup(z.local_stress, mesh_graph, None, None, True))
+            return BoundaryGradients(**vars(z), value=value(table), grad_output=torch.zeros_like(z.local_stress))
+        table, _, gy = Bd._grad(Bd._setup(fw.y, mesh_graph, None, None, True), gt, gp)
+        g = _vjp_backward(fw, mesh_graph.edge_attr, gy, scale_input)
+        return BoundaryGradients(**vars(g), value=value(table), grad_output=gy)
 
 
 @dataclass

@@ -153,16 +153,57 @@ def nodal_areas(points: torch.Tensor, faces: torch.Tensor) -> NodalAreas:
     return NodalAreas(area, ((b[1] - b[0]) * (b[3] - b[2])).reshape(1))
 
 
+class BoundaryVectors(NamedTuple):
+    """``vec`` (N, 2) float32: the lumped outward boundary vectors, 1/2 sum length * n_outward over the boundary
+    edges at a node; ``length`` (N,) float32: 1/2 sum length.  Both on the device, zero off the boundary."""
+    vec: torch.Tensor
+    length: torch.Tensor
+
+
+def boundary_vectors(points: torch.Tensor, faces: torch.Tensor) -> BoundaryVectors:
+    """The quadrature of the boundary tractions on the device (``pdg_boundary_vectors``,
+    csrc/pdg_meshfields.hip): ``sigma(n) . vec[n]`` is the nodal boundary force, the lumped traction integral;
+    to one float32 ulp of ``pdg.meshgen.boundary_vectors`` (the same fp64 terms in the same order).  One host
+    read (the status word).  Raises ValueError for a face index outside the mesh and for a boundary node with
+    other than two boundary edges; a boundary edge of a face of zero area is no error (it adds its length and no
+    vector).  Triangle meshes only."""
+    if points.device.type != "cuda" or faces.device.type != "cuda":
+        raise RuntimeError("boundary_vectors needs device tensors (the HIP path has no CPU fallback)")
+    pts = points.contiguous().float()
+    fcs = faces.contiguous().to(torch.int64)
+    if pts.dim() != 2 or pts.shape[1] not in (2, 3) or fcs.dim() != 2 or (fcs.shape[0] and fcs.shape[1] != 3):
+        raise ValueError("points must be (N, 2|3) and faces (F, 3): triangle meshes only")
+    n, dim = pts.shape
+    nf = fcs.shape[0]
+    dev = pts.device
+    nbytes = lib.pdg_boundary_vectors_scratch_bytes(n, nf)
+    if nbytes < 0:
+        raise ValueError("empty mesh, or a mesh beyond int32 indexing")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    vec = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    length = torch.empty(n, dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    lib.pdg_boundary_vectors(n, pts.data_ptr(), dim, nf, fcs.data_ptr() if nf else None, vec.data_ptr(),
+                             length.data_ptr(), status.data_ptr(), scratch.data_ptr(), nbytes, stream_handle(dev))
+    st = int(status.item())
+    if st & 1:
+        raise ValueError(f"faces hold a node index outside [0, {n})")
+    if st & 2:
+        raise ValueError("non-manifold boundary: a boundary node has other than two boundary edges")
+    return BoundaryVectors(vec, length)
+
+
 def convert_mesh_to_graph(points: torch.Tensor, faces: torch.Tensor, mean_stress,
                           node_labels: torch.Tensor | None = None, periodic: bool = True,
-                          divergence: bool = False, areas: bool = False) -> Data:
+                          divergence: bool = False, areas: bool = False, boundary: bool = False) -> Data:
     """``benchmark_gnn_fem.py:388-415`` on the device: the graph of one FEM sample, ready for
     ``EncodeProcessDecode`` (pos reduced to (x, y) float32, mean stress broadcast to every
     node, node labels as both ``surfaces_nodes_for_div`` and ``nodes_types``).  Without
     ``node_labels`` they are computed from the mesh on the device (``node_labels`` above,
     strict); ``divergence`` also sets ``op_div_matrix`` (``p1_divergence``); ``areas`` also sets
     ``node_area`` (N,) and ``cell_area`` (1,) (``nodal_areas``), the weights and the cell of the volume
-    averages of ``gnn_local_stress.homogenise``."""
+    averages of ``gnn_local_stress.homogenise``; ``boundary`` also sets ``boundary_vec`` (N, 2) and
+    ``boundary_len`` (N,) (``boundary_vectors``), the quadrature of ``gnn_local_stress.boundary``."""
     edge_index, edge_attr = mesh_graph(points, faces, periodic)
     n = points.shape[0]
     dev = points.device
@@ -177,4 +218,6 @@ def convert_mesh_to_graph(points: torch.Tensor, faces: torch.Tensor, mean_stress
         out.op_div_matrix = p1_divergence(points, faces)
     if areas:
         out.node_area, out.cell_area = nodal_areas(points, faces)
+    if boundary:
+        out.boundary_vec, out.boundary_len = boundary_vectors(points, faces)
     return out

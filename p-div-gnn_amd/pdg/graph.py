@@ -22,7 +22,8 @@ import torch
 
 from . import meshgen
 
-_NODE_KEYS = ("pos", "mean_stress", "local_stress", "nodes_types", "surfaces_nodes_for_div", "x", "node_area")
+_NODE_KEYS = ("pos", "mean_stress", "local_stress", "nodes_types", "surfaces_nodes_for_div", "x", "node_area",
+              "boundary_vec", "boundary_len")
 _EDGE_KEYS = ("edge_attr",)
 _GRAPH_KEYS = ("cell_area",)   # one entry per graph: (1,) in a Data, (B,) in a Batch
 

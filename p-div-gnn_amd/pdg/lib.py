@@ -131,12 +131,16 @@ SIGNATURES: dict[str, list] = {
     "pdg_nodal_areas": [I, P, I, I, P, P, P, P, P, ctypes.c_long, P],
     "pdg_graph_wmean": [I, P, P, I, P, P, P],
     "pdg_mean_correct": [I, P, P, P, P, P, P, P],
+    "pdg_boundary_vectors_scratch_bytes": [I, I],
+    "pdg_boundary_vectors": [I, P, I, I, P, P, P, P, P, ctypes.c_long, P],
+    "pdg_boundary_residuals": [I] + [P] * 12,
+    "pdg_boundary_residuals_bwd": [I] + [P] * 14,
 }
 # the entry points that return a value, not a status: called as they are (no error check, not counted in
 # lib.calls, not passed to lib.hook)
 _RESTYPES = {"pdg_last_error": ctypes.c_char_p, "pdg_source_hash": ctypes.c_char_p,
              "pdg_mesh_graph_scratch_bytes": ctypes.c_long, "pdg_graph_plan_scratch_bytes": ctypes.c_long,
-             "pdg_mesh_fields_scratch_bytes": ctypes.c_long,
+             "pdg_mesh_fields_scratch_bytes": ctypes.c_long, "pdg_boundary_vectors_scratch_bytes": ctypes.c_long,
              "pdg_version": c_int, "pdg_max_blocks": c_int, "pdg_wgrad_slabs_per_cu": c_int, "pdg_pq_layout": c_int}
 
 LN_STAT_BYTES = 40   # sizeof(pdg_ln_stat)

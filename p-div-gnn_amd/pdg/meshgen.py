@@ -194,6 +194,54 @@ def nodal_areas(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np.ndar
     return acc.astype(np.float32), bbox
 
 
+def boundary_vectors(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Lumped outward boundary vectors of a triangle mesh: (bvec (N, 2) float32, blen (N,) float32).  A boundary
+    edge belongs to exactly one face (``node_labels``' definition).  For the boundary edge (a, b) of face
+    (a, b, c), in the face's own vertex order, ``r = (yb - ya, -(xb - xa))`` in fp64 from the float32
+    coordinates, negated if ``r . (pc - pa) > 0``: it then points out of the material, away from the third
+    vertex, and ``r = length * n_outward``.  ``bvec[n] = 1/2 sum r_e`` and ``blen[n] = 1/2 sum |r_e|`` over the
+    boundary edges that hold n, added in ascending order of the edge's other endpoint and rounded once; a node
+    on no boundary edge gets 0.  A boundary edge of a face of zero area (``det == 0``, the ``det`` of
+    ``p1_divergence_operator``) adds its length and no vector.  ``sigma(n) . bvec[n]`` is the nodal boundary
+    force (the lumped traction integral), so ``sum bvec`` over a closed boundary is 0.  The host restatement of
+    ``pdg_boundary_vectors`` (csrc/pdg_meshfields.hip)."""
+    p32 = np.asarray(pos, dtype=np.float32)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    p = p32.astype(np.float64)
+    n = len(p)
+    seen: dict[tuple[int, int], list] = {}
+    for f, t in enumerate(faces):
+        for j in range(3):
+            a, b = int(t[j]), int(t[(j + 1) % 3])
+            seen.setdefault((min(a, b), max(a, b)), []).append((f, j))
+    ends: list[list] = [[] for _ in range(n)]    # per node: (other endpoint, item position, rx, ry, length)
+    for (u, v), uses in seen.items():
+        if len(uses) != 1:
+            continue
+        f, j = uses[0]
+        t = faces[f]
+        a, b, c = int(t[j]), int(t[(j + 1) % 3]), int(t[(j + 2) % 3])
+        rx, ry = p[b, 1] - p[a, 1], -(p[b, 0] - p[a, 0])
+        length = np.sqrt(rx * rx + ry * ry)
+        xa, ya, xb, yb, xc, yc = (*p[t[0], :2], *p[t[1], :2], *p[t[2], :2])
+        det = (xb - xa) * (yc - ya) - (xc - xa) * (yb - ya)
+        if det == 0.0:
+            rx = ry = 0.0
+        elif rx * (p[c, 0] - p[a, 0]) + ry * (p[c, 1] - p[a, 1]) > 0.0:
+            rx, ry = -rx, -ry
+        ends[u].append((v, 0, rx, ry, length))
+        ends[v].append((u, 1, rx, ry, length))
+    bvec = np.zeros((n, 2))
+    blen = np.zeros(n)
+    for i, items in enumerate(ends):
+        sx = sy = sl = 0.0
+        for _, _, rx, ry, length in sorted(items, key=lambda e: e[:2]):
+            sx, sy, sl = sx + rx, sy + ry, sl + length
+        bvec[i] = 0.5 * sx, 0.5 * sy
+        blen[i] = 0.5 * sl
+    return bvec.astype(np.float32), blen.astype(np.float32)
+
+
 def node_labels(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, int, int]:
     """``compute_node_labels`` (``datasets.py:122-179``) from the mesh alone: (labels (N,) int64,
     boundary components, external ones).  A boundary edge belongs to exactly one face; the
