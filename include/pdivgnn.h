@@ -474,6 +474,16 @@ long pdg_mesh_graph_scratch_bytes(int n_nodes, int n_faces);
 int pdg_mesh_graph(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
                    int periodic, int64_t* edge_rows, int64_t* edge_cols, float* edge_attr,
                    long capacity, int* n_edges, void* scratch, long scratch_bytes, void* stream);
+/* The same for faces of nv vertices, (n_faces, nv) int64: nv == 3 is pdg_mesh_graph, bitwise, with its
+ * scratch size; nv == 4 is a quad mesh, whose edges are the four sides (f0,f1) (f1,f2) (f2,f3) (f0,f3)
+ * of every quad and never a diagonal (convert_utils.py:63-81, _quad_face_to_edge).  `capacity` >=
+ * 2 nv n_faces (+ 4 PDG_SIDE_MAX + 4 when periodic).  Any other nv is refused on the host (the size
+ * function returns < 0).  Both calls: a face with an index outside [0, n_nodes) is never dereferenced;
+ * its edges are dropped and *n_edges = -2 reports it. */
+long pdg_mesh_graph_cells_scratch_bytes(int n_nodes, int n_faces, int nv);
+int pdg_mesh_graph_cells(int n_nodes, const float* points, int dim, int n_faces, int nv, const int64_t* faces,
+                         int periodic, int64_t* edge_rows, int64_t* edge_cols, float* edge_attr,
+                         long capacity, int* n_edges, void* scratch, long scratch_bytes, void* stream);
 
 /* Backward of the P/Q gathers: gP[v] = sum_{dst-seg(v)} gz1m + sum_{src-seg(v)} gz1e,
  * gQ[v] = sum_{src-seg(v)} gz1m + sum_{dst-seg(v)} gz1e.  src-seg uses rowptr_src and
@@ -841,6 +851,34 @@ int pdg_p1_div_operator(int n_nodes, const float* points, int dim, int n_faces, 
 long pdg_boundary_vectors_scratch_bytes(int n_nodes, int n_faces);
 int pdg_boundary_vectors(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces, float* bvec,
                          float* blen, int* status, void* scratch, long scratch_bytes, void* stream);
+
+/* The mesh fields for faces of nv vertices, (n_faces, nv) int64 in the face's own vertex order (either
+ * orientation): the same kernels as templates on nv.  nv == 3 gives bitwise what the calls above give, with
+ * their scratch sizes; nv == 4 is a quad mesh (a, b, c, d), the restatements being pdg/meshgen.py's quad
+ * branches.  Any other nv is refused on the host (the size functions return < 0), as are sizes with
+ * nv^2 n_faces + 1024 >= 2^31.  Outputs, status bits, host checks and capture as for the calls above.  For a quad:
+ *   edges     the four sides (a,b) (b,c) (c,d) (d,a), never a diagonal: a boundary edge is a side of one face;
+ *   det       (xc-xa)(yd-yb) - (xd-xb)(yc-ya), the diagonals' cross product = 2 x the signed area; area = |det| / 2;
+ *   operator  pdg_div_operator_cells, the Q1 counterpart of pdg_p1_div_operator with the face's mean Q1 gradients
+ *             gx = (yb-yd, yc-ya, yd-yb, ya-yc) / det, gy = (xd-xb, xa-xc, xb-xd, xc-xa) / det: area g[vn] is the
+ *             integral of grad N_vn over the face for the bilinear shape functions of any quad.  nv^2 (row, column
+ *             node) pairs per face, so `capacity` >= 2 nv^2 n_faces (32 per quad); det == 0 is status bit 1;
+ *   areas     area[n] = sum over the faces of the integral of N_n = (|det| + sgn(det) t_k) / 12 at the face's corner
+ *             k, t_k = (x[k+1]-x[k])(y[k-1]-y[k]) - (y[k+1]-y[k])(x[k-1]-x[k]) (twice the signed corner triangle):
+ *             area / 4 on a parallelogram, and what a 2 x 2 Gauss rule gathers to the nodes; det == 0 adds 0;
+ *   vectors   the side (v_j, v_j+1) is oriented away from v_j+2; det == 0 is status bit 4. */
+long pdg_mesh_fields_cells_scratch_bytes(int n_nodes, int n_faces, int nv);
+int pdg_node_labels_cells(int n_nodes, const float* points, int dim, int n_faces, int nv, const int64_t* faces,
+                          int64_t* labels, int* info, void* scratch, long scratch_bytes, void* stream);
+int pdg_div_operator_cells(int n_nodes, const float* points, int dim, int n_faces, int nv, const int64_t* faces,
+                           int64_t* rows, int64_t* cols, float* vals, long capacity, int* nnz, int* status,
+                           void* scratch, long scratch_bytes, void* stream);
+int pdg_nodal_areas_cells(int n_nodes, const float* points, int dim, int n_faces, int nv, const int64_t* faces,
+                          float* area, float* bbox, int* status, void* scratch, long scratch_bytes, void* stream);
+long pdg_boundary_vectors_cells_scratch_bytes(int n_nodes, int n_faces, int nv);
+int pdg_boundary_vectors_cells(int n_nodes, const float* points, int dim, int n_faces, int nv, const int64_t* faces,
+                               float* bvec, float* blen, int* status, void* scratch, long scratch_bytes,
+                               void* stream);
 
 /* ---------------------------------------------------------------- boundary residuals */
 /* What a plane-stress field does on the boundary of the periodic cell (pdg_boundary.hip), built like the

@@ -1,7 +1,9 @@
 // Mesh graph construction on the device: the "with preprocessing"
 // path of the reference (benchmark_gnn_fem.py:388-415, datasets.py:247-263):
-//   mesh_to_graph     (convert_utils.py:47-60, PyG FaceToEdge: the 3 edges of every
-//                      triangle in both directions, coalesced),
+//   mesh_to_graph     (convert_utils.py:47-81, PyG FaceToEdge: the 3 edges of every
+//                      triangle in both directions, coalesced; _quad_face_to_edge: the 4
+//                      sides of every quad, never a diagonal -- the kernels that read a
+//                      face are templates on NV, the vertices per face),
 //   edge lengths      (datasets.py:182-188, |pos[row] - pos[col]| over all coordinates),
 //   compute_periodic_graph (datasets.py:39-119: left<->right and lower<->upper side nodes
 //                      paired in (y, x) order, the 4 corners paired with the opposite
@@ -21,7 +23,8 @@
 // The side lists are sorted by one workgroup (bitonic, in LDS): each side holds at most
 // PDG_SIDE_MAX nodes (a 4096 x 4096 grid).  Invalid periodic geometry (unequal opposite
 // sides, a corner that is not exactly one node, a side longer than PDG_SIDE_MAX) is
-// reported as *n_edges = -1.
+// reported as *n_edges = -1.  A face with an index outside [0, n_nodes) is never dereferenced:
+// its edges are dropped (validity is decided per face) and *n_edges = -2 reports it.
 #include <cfloat>
 
 #include "pdg_bbox.hpp"     // bbox_kernel, bbox_load
@@ -44,7 +47,7 @@ constexpr int SORT_THREADS = 1024;
 // Scratch layout (int32 words unless noted), see pdg_mesh_graph_scratch_bytes.
 struct Scratch {
   float* bbox;     // [GT_BLOCKS_MAX][4] per-block (min x, min y, max x, max y)
-  int* ctr;        // [16]: side counts (4), corner counts (4), corners (4), npairs, error
+  int* ctr;        // [16]: side counts (4), corner counts (4), corners (4), npairs, error, face out of range
   int* side;       // [4][SIDE_MAX]
   int* prow;       // [2 * 2 * SIDE_MAX + 4]
   int* pcol;
@@ -52,7 +55,7 @@ struct Scratch {
   int* fill;       // [N]
   int* ucnt;       // [N + 1] -> row pointer of the result
   int* bsum;       // [scan blocks + 1]
-  int* nb;         // [6F + pairs] slot array: 2 * col + (1 if periodic else 0)
+  int* nb;         // [2 NV F + pairs] slot array: 2 * col + (1 if periodic else 0)
 };
 
 __device__ __forceinline__ float nmul(float a, float b) { return __fmul_rn(a, b); }
@@ -163,48 +166,61 @@ __global__ __launch_bounds__(SORT_THREADS) void pairs_kernel(const float* __rest
   if (threadIdx.x == 0) ctr[12] = 2 * nl + 2 * nd + 4;
 }
 
-// Directed edges of face f: (a,b) (b,a) (b,c) (c,b) (a,c) (c,a) -- FaceToEdge's three edges,
-// made undirected.  Pairs k: (prow[k], pcol[k]).
-__device__ __forceinline__ void face_edge(const int64_t* __restrict__ faces, int f, int j, int& u, int& v) {
-  const int64_t* t = faces + 3 * (size_t)f;
-  const int a = (int)t[0], b = (int)t[1], c = (int)t[2];
-  switch (j) {
-    case 0: u = a; v = b; break;
-    case 1: u = b; v = a; break;
-    case 2: u = b; v = c; break;
-    case 3: u = c; v = b; break;
-    case 4: u = a; v = c; break;
-    default: u = c; v = a; break;
-  }
+// Directed edge j of face f, j = 2 * side + direction: the sides (0,1) (1,2) .. (NV-2,NV-1) (0,NV-1), each in
+// both directions -- (a,b) (b,a) (b,c) (c,b) (a,c) (c,a) of a triangle (FaceToEdge's three edges, made undirected),
+// (f0,f1) (f1,f2) (f2,f3) (f0,f3) and their reverses of a quad (_quad_face_to_edge).  False for a face with an index
+// outside [0, n): nothing of it is used.  Pairs k: (prow[k], pcol[k]).
+template <int NV>
+__device__ __forceinline__ bool face_edge(const int64_t* __restrict__ faces, int n, int f, int j, int& u, int& v) {
+  const int64_t* t = faces + NV * (size_t)f;
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) ok = ok && t[i] >= 0 && t[i] < n;
+  if (!ok) return false;
+  const int s = j >> 1;
+  const int a = (int)t[s == NV - 1 ? 0 : s], b = (int)t[s == NV - 1 ? NV - 1 : s + 1];
+  u = (j & 1) ? b : a;
+  v = (j & 1) ? a : b;
+  return true;
 }
 
-__global__ __launch_bounds__(GT) void count_kernel(int n, int nf, const int64_t* __restrict__ faces,
-                                                   const int* __restrict__ ctr, const int* __restrict__ prow,
-                                                   int* __restrict__ deg, int* __restrict__ fill, int periodic) {
+template <int NV>
+__global__ __launch_bounds__(GT) void count_kernel(int n, int nf, const int64_t* __restrict__ faces, int* ctr,
+                                                   const int* __restrict__ prow, int* __restrict__ deg,
+                                                   int* __restrict__ fill, int periodic) {
   const int np = periodic && !ctr[13] ? ctr[12] : 0;
-  const long total = 6L * nf + np;
+  const long ne = 2L * NV * nf;
+  const long total = ne + np;
   for (long k = (long)blockIdx.x * GT + threadIdx.x; k < total; k += (long)gridDim.x * GT) {
     int u, v;
-    if (k < 6L * nf) face_edge(faces, (int)(k / 6), (int)(k % 6), u, v);
-    else u = prow[k - 6L * nf];
+    if (k < ne) {
+      if (!face_edge<NV>(faces, n, (int)(k / (2 * NV)), (int)(k % (2 * NV)), u, v)) {
+        ctr[14] = 1;   // every writer stores the same value; read by finish_kernel, launches later
+        continue;
+      }
+    } else {
+      u = prow[k - ne];
+    }
     atomicAdd(&deg[u], 1);
   }
   for (int i = blockIdx.x * GT + threadIdx.x; i < n; i += gridDim.x * GT) fill[i] = 0;
 }
 
-__global__ __launch_bounds__(GT) void fill_kernel(int nf, const int64_t* __restrict__ faces, const int* __restrict__ ctr,
-                                                  const int* __restrict__ prow, const int* __restrict__ pcol,
-                                                  const int* __restrict__ off, int* __restrict__ fill,
-                                                  int* __restrict__ nb, int periodic) {
+template <int NV>
+__global__ __launch_bounds__(GT) void fill_kernel(int n, int nf, const int64_t* __restrict__ faces,
+                                                  const int* __restrict__ ctr, const int* __restrict__ prow,
+                                                  const int* __restrict__ pcol, const int* __restrict__ off,
+                                                  int* __restrict__ fill, int* __restrict__ nb, int periodic) {
   const int np = periodic && !ctr[13] ? ctr[12] : 0;
-  const long total = 6L * nf + np;
+  const long ne = 2L * NV * nf;
+  const long total = ne + np;
   for (long k = (long)blockIdx.x * GT + threadIdx.x; k < total; k += (long)gridDim.x * GT) {
     int u, v, flag = 0;
-    if (k < 6L * nf) {
-      face_edge(faces, (int)(k / 6), (int)(k % 6), u, v);
+    if (k < ne) {
+      if (!face_edge<NV>(faces, n, (int)(k / (2 * NV)), (int)(k % (2 * NV)), u, v)) continue;
     } else {
-      u = prow[k - 6L * nf];
-      v = pcol[k - 6L * nf];
+      u = prow[k - ne];
+      v = pcol[k - ne];
       flag = 1;
     }
     nb[off[u] + atomicAdd(&fill[u], 1)] = 2 * v + flag;
@@ -265,12 +281,12 @@ __global__ __launch_bounds__(GT) void emit_kernel(int n, const float* __restrict
 
 __global__ void finish_kernel(int n, const int* __restrict__ ctr, const int* __restrict__ rowptr, int periodic,
                               int* __restrict__ n_edges) {
-  *n_edges = periodic && ctr[13] ? -1 : rowptr[n];
+  *n_edges = ctr[14] ? -2 : periodic && ctr[13] ? -1 : rowptr[n];
 }
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-size_t layout(int n, int nf, Scratch* s, char* base) {
+size_t layout(int n, int nf, int nv, Scratch* s, char* base) {
   size_t o = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + o : nullptr;
@@ -288,7 +304,7 @@ size_t layout(int n, int nf, Scratch* s, char* base) {
   int* fill = (int*)take(sizeof(int) * (size_t)n);
   int* ucnt = (int*)take(sizeof(int) * ((size_t)n + 1));
   int* bsum = (int*)take(sizeof(int) * (size_t)(nscan + 1));
-  int* nbp = (int*)take(sizeof(int) * (6 * (size_t)nf + pmax));
+  int* nbp = (int*)take(sizeof(int) * (2 * (size_t)nv * (size_t)nf + pmax));
   if (s) *s = Scratch{bbox, ctr, side, prow, pcol, deg, fill, ucnt, bsum, nbp};
   return o;
 }
@@ -299,27 +315,12 @@ int grid_for(long work) {
   return (int)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
-}  // namespace
-
-extern "C" long pdg_mesh_graph_scratch_bytes(int n_nodes, int n_faces) {
-  if (n_nodes <= 0 || n_faces < 0) return -1;
-  return (long)layout(n_nodes, n_faces, nullptr, nullptr);
-}
-
-extern "C" int pdg_mesh_graph(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
-                              int periodic, int64_t* edge_rows, int64_t* edge_cols, float* edge_attr, long capacity,
-                              int* n_edges, void* scratch, long scratch_bytes, void* stream) {
-  PDG_CHECK_ARG(n_nodes > 0 && n_faces >= 0 && (dim == 2 || dim == 3), "pdg_mesh_graph: bad sizes");
-  PDG_CHECK_ARG(points && edge_rows && edge_cols && edge_attr && n_edges && scratch && (faces || n_faces == 0),
-                "pdg_mesh_graph: null argument");
-  PDG_CHECK_ARG(scratch_bytes >= pdg_mesh_graph_scratch_bytes(n_nodes, n_faces), "pdg_mesh_graph: scratch too small");
-  PDG_CHECK_ARG(capacity >= 6L * n_faces + (periodic ? 4L * SIDE_MAX + 4 : 0),
-                "pdg_mesh_graph: capacity below 6 * faces (+ periodic pairs)");
-  PDG_CHECK_ARG((long)n_nodes * 2 + 1 < 0x7fffffffL && 6L * n_faces + 4L * SIDE_MAX + 4 < 0x7fffffffL,
-                "pdg_mesh_graph: sizes beyond int32 indexing");
-  hipStream_t st = (hipStream_t)stream;
+template <int NV>
+void graph_launch(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces, int periodic,
+                  int64_t* edge_rows, int64_t* edge_cols, float* edge_attr, int* n_edges, void* scratch,
+                  hipStream_t st) {
   Scratch s;
-  layout(n_nodes, n_faces, &s, (char*)scratch);
+  layout(n_nodes, n_faces, NV, &s, (char*)scratch);
   const int nbb = bbox_blocks(n_nodes);
   hipLaunchKernelGGL(bbox_kernel, dim3(nbb), dim3(BBOX_T), 0, st, n_nodes, points, dim, s.bbox, s.ctr);
   if (periodic) {
@@ -328,17 +329,68 @@ extern "C" int pdg_mesh_graph(int n_nodes, const float* points, int dim, int n_f
     hipLaunchKernelGGL(pairs_kernel, dim3(1), dim3(SORT_THREADS), 0, st, points, dim, s.ctr, s.side, s.prow, s.pcol);
   }
   (void)hipMemsetAsync(s.deg, 0, sizeof(int) * ((size_t)n_nodes + 1), st);
-  const long work = 6L * n_faces + (periodic ? 4L * SIDE_MAX + 4 : 0);
-  hipLaunchKernelGGL(count_kernel, dim3(grid_for(std::max<long>(work, n_nodes))), dim3(GT), 0, st, n_nodes, n_faces,
-                     faces, s.ctr, s.prow, s.deg, s.fill, periodic);
+  const long work = 2L * NV * n_faces + (periodic ? 4L * SIDE_MAX + 4 : 0);
+  hipLaunchKernelGGL(count_kernel<NV>, dim3(grid_for(std::max<long>(work, n_nodes))), dim3(GT), 0, st, n_nodes,
+                     n_faces, faces, s.ctr, s.prow, s.deg, s.fill, periodic);
   scan(n_nodes, s.deg, s.bsum, st);
-  hipLaunchKernelGGL(fill_kernel, dim3(grid_for(work)), dim3(GT), 0, st, n_faces, faces, s.ctr, s.prow, s.pcol, s.deg,
-                     s.fill, s.nb, periodic);
+  hipLaunchKernelGGL(fill_kernel<NV>, dim3(grid_for(work)), dim3(GT), 0, st, n_nodes, n_faces, faces, s.ctr, s.prow,
+                     s.pcol, s.deg, s.fill, s.nb, periodic);
   hipLaunchKernelGGL(row_sort_kernel, dim3(grid_for(n_nodes)), dim3(GT), 0, st, n_nodes, s.deg, s.nb, s.ucnt);
   scan(n_nodes, s.ucnt, s.bsum, st);
   hipLaunchKernelGGL(emit_kernel, dim3(grid_for(n_nodes)), dim3(GT), 0, st, n_nodes, points, dim, s.deg, s.nb, s.ucnt,
                      edge_rows, edge_cols, edge_attr);
   hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(1), 0, st, n_nodes, s.ctr, s.ucnt, periodic, n_edges);
-  PDG_CHECK_LAUNCH("pdg_mesh_graph");
+}
+
+long graph_bytes(int n_nodes, int n_faces, int nv) {
+  if (n_nodes <= 0 || n_faces < 0 || (nv != 3 && nv != 4)) return -1;
+  return (long)layout(n_nodes, n_faces, nv, nullptr, nullptr);
+}
+
+// Every check runs on the host before any HIP call, under the entry point's own name.
+int graph_run(const char* name, int nv, int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+              int periodic, int64_t* edge_rows, int64_t* edge_cols, float* edge_attr, long capacity, int* n_edges,
+              void* scratch, long scratch_bytes, void* stream) {
+  PDG_CHECK_ARG(nv == 3 || nv == 4, "%s: nv must be 3 (triangles) or 4 (quads), got %d", name, nv);
+  PDG_CHECK_ARG(n_nodes > 0 && n_faces >= 0 && (dim == 2 || dim == 3), "%s: bad sizes", name);
+  PDG_CHECK_ARG(points && edge_rows && edge_cols && edge_attr && n_edges && scratch && (faces || n_faces == 0),
+                "%s: null argument", name);
+  PDG_CHECK_ARG((long)n_nodes * 2 + 1 < 0x7fffffffL && 2L * nv * n_faces + 4L * SIDE_MAX + 4 < 0x7fffffffL,
+                "%s: sizes beyond int32 indexing", name);
+  PDG_CHECK_ARG(scratch_bytes >= graph_bytes(n_nodes, n_faces, nv), "%s: scratch too small", name);
+  PDG_CHECK_ARG(capacity >= 2L * nv * n_faces + (periodic ? 4L * SIDE_MAX + 4 : 0),
+                "%s: capacity below %d * faces (+ periodic pairs)", name, 2 * nv);
+  hipStream_t st = (hipStream_t)stream;
+  if (nv == 3)
+    graph_launch<3>(n_nodes, points, dim, n_faces, faces, periodic, edge_rows, edge_cols, edge_attr, n_edges, scratch,
+                    st);
+  else
+    graph_launch<4>(n_nodes, points, dim, n_faces, faces, periodic, edge_rows, edge_cols, edge_attr, n_edges, scratch,
+                    st);
+  PDG_CHECK_LAUNCH(name);
   return PDG_OK;
+}
+
+}  // namespace
+
+extern "C" long pdg_mesh_graph_scratch_bytes(int n_nodes, int n_faces) { return graph_bytes(n_nodes, n_faces, 3); }
+
+extern "C" int pdg_mesh_graph(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                              int periodic, int64_t* edge_rows, int64_t* edge_cols, float* edge_attr, long capacity,
+                              int* n_edges, void* scratch, long scratch_bytes, void* stream) {
+  return graph_run("pdg_mesh_graph", 3, n_nodes, points, dim, n_faces, faces, periodic, edge_rows, edge_cols,
+                   edge_attr, capacity, n_edges, scratch, scratch_bytes, stream);
+}
+
+// The same call for faces of nv vertices: (n_faces, nv) int64, nv == 3 (bitwise the call above) or 4.
+extern "C" long pdg_mesh_graph_cells_scratch_bytes(int n_nodes, int n_faces, int nv) {
+  return graph_bytes(n_nodes, n_faces, nv);
+}
+
+extern "C" int pdg_mesh_graph_cells(int n_nodes, const float* points, int dim, int n_faces, int nv,
+                                    const int64_t* faces, int periodic, int64_t* edge_rows, int64_t* edge_cols,
+                                    float* edge_attr, long capacity, int* n_edges, void* scratch, long scratch_bytes,
+                                    void* stream) {
+  return graph_run("pdg_mesh_graph_cells", nv, n_nodes, points, dim, n_faces, faces, periodic, edge_rows, edge_cols,
+                   edge_attr, capacity, n_edges, scratch, scratch_bytes, stream);
 }

@@ -1,5 +1,10 @@
-// Per-node fields of a bare triangle mesh on the device: what the reference's published
+// Per-node fields of a bare triangle or quad mesh on the device: what the reference's published
 // workload derives on the host before the model runs, and what the divergence check needs.
+// Every kernel that reads a face is a template on NV, the vertices per face (3 or 4): the triangle
+// instances are the code the triangle entry points always ran, the quad instances serve the *_cells
+// entry points (pdg/meshgen.py's quad restatements: the four sides, never a diagonal; the mean Q1
+// gradients; the exact Q1 nodal integrals).  Below, the counts are written for triangles: read NV for
+// 3 and NV^2 for 9.
 //
 //   pdg_node_labels      compute_node_labels (datasets.py:122-179): +1 on the external boundary,
 //                        -1 on an internal boundary (a hole's rim), 0 elsewhere
@@ -95,14 +100,14 @@ struct BvecScratch {
   u64* sorted2;  // [6F] the boundary edges' endpoints by node
 };
 
-size_t label_layout(int n, int nf, LabelScratch* s, char* base) {
+size_t label_layout(int n, int nf, int nv, LabelScratch* s, char* base) {
   size_t o = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + o : nullptr;
     o += align_up(bytes);
     return p;
   };
-  const size_t e = 3 * (size_t)std::max(nf, 1);
+  const size_t e = (size_t)nv * (size_t)std::max(nf, 1);
   LabelScratch t;
   t.bbox = (float*)take(4 * sizeof(float) * BBOX_BLOCKS);
   t.ctr = (int*)take(16 * sizeof(int));
@@ -118,14 +123,14 @@ size_t label_layout(int n, int nf, LabelScratch* s, char* base) {
   return o;
 }
 
-size_t bvec_layout(int n, int nf, BvecScratch* s, char* base) {
+size_t bvec_layout(int n, int nf, int nv, BvecScratch* s, char* base) {
   size_t o = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + o : nullptr;
     o += align_up(bytes);
     return p;
   };
-  const size_t e = 3 * (size_t)std::max(nf, 1);
+  const size_t e = (size_t)nv * (size_t)std::max(nf, 1);
   BvecScratch t;
   t.zero = (int*)take(sizeof(int) * (4 * (size_t)n + 2));
   t.bsum = (int*)take(sizeof(int) * scan_bsum_len(n));
@@ -138,14 +143,14 @@ size_t bvec_layout(int n, int nf, BvecScratch* s, char* base) {
   return o;
 }
 
-size_t div_layout(int n, int nf, DivScratch* s, char* base) {
+size_t div_layout(int n, int nf, int nv, DivScratch* s, char* base) {
   size_t o = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + o : nullptr;
     o += align_up(bytes);
     return p;
   };
-  const size_t e = 9 * (size_t)std::max(nf, 1);
+  const size_t e = (size_t)(nv * nv) * (size_t)std::max(nf, 1);
   DivScratch t;
   t.zero = (int*)take(sizeof(int) * (3 * (size_t)n + 2));
   t.bsum = (int*)take(sizeof(int) * scan_bsum_len(n));
@@ -156,30 +161,43 @@ size_t div_layout(int n, int nf, DivScratch* s, char* base) {
   return o;
 }
 
-bool sizes_ok(int n_nodes, int n_faces) {
-  // the scan indexes base + i < n + SCAN_BLOCK in int32; an item position (< 9 F) fills a slot's low word
-  return n_nodes > 0 && n_faces >= 0 && (long)n_nodes + SCAN_BLOCK < 0x7fffffffL &&
-         9L * n_faces + SCAN_BLOCK < 0x7fffffffL;
+bool sizes_ok(int n_nodes, int n_faces, int nv) {
+  // the scan indexes base + i < n + SCAN_BLOCK in int32; an item position (< nv^2 F) fills a slot's low word
+  return (nv == 3 || nv == 4) && n_nodes > 0 && n_faces >= 0 && (long)n_nodes + SCAN_BLOCK < 0x7fffffffL &&
+         (long)(nv * nv) * n_faces + SCAN_BLOCK < 0x7fffffffL;
 }
 
+template <int NV>
 __device__ __forceinline__ bool in_range(const int64_t* __restrict__ t, int n) {
-  return t[0] >= 0 && t[0] < n && t[1] >= 0 && t[1] < n && t[2] >= 0 && t[2] < n;
+  bool ok = true;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) ok = ok && t[v] >= 0 && t[v] < n;
+  return ok;
+}
+
+// The vertex after / before vertex v in the face's own cyclic order.
+template <int NV>
+__device__ __forceinline__ unsigned next_of(unsigned v) {
+  return v == NV - 1 ? 0 : v + 1;
+}
+template <int NV>
+__device__ __forceinline__ unsigned prev_of(unsigned v) {
+  return v == 0 ? NV - 1 : v - 1;
 }
 
 // ----------------------------------------------------------------------------------- labels
+template <int NV>
 __global__ __launch_bounds__(PT) void label_face_kernel(int nf, const int64_t* __restrict__ faces, int n,
                                                         int* __restrict__ fok, int* __restrict__ cnt,
                                                         int* __restrict__ status) {
   int bad = 0;
   for (long f = (long)blockIdx.x * PT + threadIdx.x; f < nf; f += (long)gridDim.x * PT) {
-    const int64_t* t = faces + 3 * f;
-    const int ok = in_range(t, n);
+    const int64_t* t = faces + NV * f;
+    const int ok = in_range<NV>(t, n);
     fok[f] = ok;
     if (ok) {
-      const int a = (int)t[0], b = (int)t[1], c = (int)t[2];
-      atomicAdd(&cnt[min(a, b)], 1);
-      atomicAdd(&cnt[min(b, c)], 1);
-      atomicAdd(&cnt[min(c, a)], 1);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) atomicAdd(&cnt[min((int)t[j], (int)t[j == NV - 1 ? 0 : j + 1])], 1);
     } else {
       bad = 1;
     }
@@ -187,16 +205,18 @@ __global__ __launch_bounds__(PT) void label_face_kernel(int nf, const int64_t* _
   if (bad) atomicOr(status, ST_RANGE);   // ST_RANGE == BV_RANGE
 }
 
-// Undirected edge j of face f (j = i % 3: (0,1), (1,2), (2,0)) under its smaller endpoint.
+// Undirected edge j of face f (j = i % NV: the side (j, j + 1), cyclic; (0,1), (1,2), (2,0) of a triangle) under its
+// smaller endpoint.
+template <int NV>
 struct EdgeByMin {
   const int64_t* faces;
   const int* fok;
   u64* sorted;
   __device__ bool item(long i, int& major, unsigned& minor) const {
-    const long f = i / 3;
+    const long f = i / NV;
     if (!fok[f]) return false;
-    const int j = (int)(i - 3 * f);
-    const int a = (int)faces[3 * f + j], b = (int)faces[3 * f + (j == 2 ? 0 : j + 1)];
+    const int j = (int)(i - NV * f);
+    const int a = (int)faces[NV * f + j], b = (int)faces[NV * f + (j == NV - 1 ? 0 : j + 1)];
     major = min(a, b);
     minor = (unsigned)max(a, b);
     return true;
@@ -329,57 +349,77 @@ __global__ __launch_bounds__(PT) void labels_kernel(int n, const int* __restrict
 }
 
 // --------------------------------------------------------------------------------- operator
-struct Tri {
-  double xa, ya, xb, yb, xc, yc, det;
+template <int NV>
+struct Cell {
+  double x[NV], y[NV], det;
 };
 
-// meshgen.p1_divergence_operator's fp64 expressions, one rounding per operation.
-__device__ __forceinline__ Tri triangle(const float* __restrict__ p, int dim, const int64_t* __restrict__ t) {
+// A vertex's coordinate by a run-time index: selects over registers (the loops are unrolled), no indexed array.
+template <int NV>
+__device__ __forceinline__ double pick(const double (&a)[NV], unsigned k) {
+  double r = a[0];
+#pragma unroll
+  for (int v = 1; v < NV; ++v) r = k == (unsigned)v ? a[v] : r;
+  return r;
+}
+
+// meshgen.p1_divergence_operator's / q1_divergence_operator's fp64 expressions, one rounding per operation.
+// det = 2 * signed area: (xb - xa)(yc - ya) - (xc - xa)(yb - ya) of a triangle, the diagonals' cross product
+// (xc - xa)(yd - yb) - (xd - xb)(yc - ya) of a quad.
+template <int NV>
+__device__ __forceinline__ Cell<NV> cell(const float* __restrict__ p, int dim, const int64_t* __restrict__ t) {
 #pragma clang fp contract(off)
-  Tri q;
-  q.xa = p[(size_t)t[0] * dim];
-  q.ya = p[(size_t)t[0] * dim + 1];
-  q.xb = p[(size_t)t[1] * dim];
-  q.yb = p[(size_t)t[1] * dim + 1];
-  q.xc = p[(size_t)t[2] * dim];
-  q.yc = p[(size_t)t[2] * dim + 1];
-  const double m0 = (q.xb - q.xa) * (q.yc - q.ya);
-  const double m1 = (q.xc - q.xa) * (q.yb - q.ya);
-  q.det = m0 - m1;   // 2 * signed area
+  Cell<NV> q;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    q.x[v] = p[(size_t)t[v] * dim];
+    q.y[v] = p[(size_t)t[v] * dim + 1];
+  }
+  if constexpr (NV == 3) {
+    const double m0 = (q.x[1] - q.x[0]) * (q.y[2] - q.y[0]);
+    const double m1 = (q.x[2] - q.x[0]) * (q.y[1] - q.y[0]);
+    q.det = m0 - m1;
+  } else {
+    const double m0 = (q.x[2] - q.x[0]) * (q.y[3] - q.y[1]);
+    const double m1 = (q.x[3] - q.x[1]) * (q.y[2] - q.y[0]);
+    q.det = m0 - m1;
+  }
   return q;
 }
 
+template <int NV>
 __global__ __launch_bounds__(PT) void div_face_kernel(int nf, const int64_t* __restrict__ faces, int n,
                                                       const float* __restrict__ p, int dim, int* __restrict__ fok,
                                                       int* __restrict__ cnt, int* __restrict__ status) {
   int bad = 0;
   for (long f = (long)blockIdx.x * PT + threadIdx.x; f < nf; f += (long)gridDim.x * PT) {
-    const int64_t* t = faces + 3 * f;
-    int ok = in_range(t, n);
+    const int64_t* t = faces + NV * f;
+    int ok = in_range<NV>(t, n);
     if (!ok) {
       bad |= DV_RANGE;
-    } else if (triangle(p, dim, t).det == 0.0) {
+    } else if (cell<NV>(p, dim, t).det == 0.0) {
       bad |= DV_DEGENERATE;
       ok = 0;
     }
     fok[f] = ok;
     if (ok)
-      for (int v = 0; v < 3; ++v) atomicAdd(&cnt[(int)t[v]], 3);
+      for (int v = 0; v < NV; ++v) atomicAdd(&cnt[(int)t[v]], NV);
   }
   if (bad) atomicOr(status, bad);
 }
 
-// Item i = 9 f + 3 vi + vn: face f's contribution to row faces[f][vi] at column node faces[f][vn].
+// Item i = NV^2 f + NV vi + vn: face f's contribution to row faces[f][vi] at column node faces[f][vn].
+template <int NV>
 struct PairByRow {
   const int64_t* faces;
   const int* fok;
   u64* sorted;
   __device__ bool item(long i, int& major, unsigned& minor) const {
-    const long f = i / 9;
+    const long f = i / (NV * NV);
     if (!fok[f]) return false;
-    const int r = (int)(i - 9 * f);
-    major = (int)faces[3 * f + r / 3];
-    minor = (unsigned)faces[3 * f + r % 3];
+    const int r = (int)(i - NV * NV * f);
+    major = (int)faces[NV * f + r / NV];
+    minor = (unsigned)faces[NV * f + r % NV];
     return true;
   }
   __device__ void emit(long k, int, u64 slot) const { sorted[k] = slot; }
@@ -396,6 +436,7 @@ __global__ __launch_bounds__(PT) void div_count_kernel(int n, const int* __restr
 }
 
 // Row r: its distinct column nodes c_0 < c_1 < ... give the entries (r, c_j) then (r, c_j + N).
+template <int NV>
 __global__ __launch_bounds__(PT) void div_emit_kernel(int n, const float* __restrict__ p, int dim,
                                                       const int64_t* __restrict__ faces,
                                                       const int* __restrict__ rowptr, const u64* __restrict__ sorted,
@@ -411,8 +452,8 @@ __global__ __launch_bounds__(PT) void div_emit_kernel(int n, const float* __rest
     double wsum = 0.0;
     for (int k = b; k < e; ++k) {
       const unsigned id = (unsigned)(sorted[k] & 0xffffffffu);
-      const unsigned f = id / 9, q = id - 9 * f;
-      if (q / 3 == q % 3) wsum += 0.5 * fabs(triangle(p, dim, faces + 3 * (size_t)f).det);
+      const unsigned f = id / (NV * NV), q = id - NV * NV * f;
+      if (q / NV == q % NV) wsum += 0.5 * fabs(cell<NV>(p, dim, faces + NV * (size_t)f).det);
     }
     const long o = 2L * uptr[r];
     int j = 0;
@@ -421,11 +462,14 @@ __global__ __launch_bounds__(PT) void div_emit_kernel(int n, const float* __rest
       double ax = 0.0, ay = 0.0;
       for (; k < e && (unsigned)(sorted[k] >> 32) == c; ++k) {
         const unsigned id = (unsigned)(sorted[k] & 0xffffffffu);
-        const unsigned f = id / 9, vn = (id - 9 * f) % 3;
-        const Tri t = triangle(p, dim, faces + 3 * (size_t)f);
+        const unsigned f = id / (NV * NV), vn = (id - NV * NV * f) % NV;
+        const Cell<NV> t = cell<NV>(p, dim, faces + NV * (size_t)f);
         const double area = 0.5 * fabs(t.det);
-        const double dy = vn == 0 ? t.yb - t.yc : vn == 1 ? t.yc - t.ya : t.ya - t.yb;
-        const double dx = vn == 0 ? t.xc - t.xb : vn == 1 ? t.xa - t.xc : t.xb - t.xa;
+        // area * g[vn] = the integral of grad N_vn over the face: (y[vn + 1] - y[vn - 1], x[vn - 1] - x[vn + 1]) / 2,
+        // the P1 gradient of a triangle and the mean Q1 gradient of a quad
+        const unsigned nx = next_of<NV>(vn), pv = prev_of<NV>(vn);
+        const double dy = pick<NV>(t.y, nx) - pick<NV>(t.y, pv);
+        const double dx = pick<NV>(t.x, pv) - pick<NV>(t.x, nx);
         ax += area * (dy / t.det) / wsum;
         ay += area * (dx / t.det) / wsum;
       }
@@ -440,30 +484,32 @@ __global__ __launch_bounds__(PT) void div_emit_kernel(int n, const float* __rest
 }
 
 // ------------------------------------------------------------------------------ nodal areas
+template <int NV>
 __global__ __launch_bounds__(PT) void area_face_kernel(int nf, const int64_t* __restrict__ faces, int n,
                                                        int* __restrict__ fok, int* __restrict__ cnt,
                                                        int* __restrict__ status) {
   int bad = 0;
   for (long f = (long)blockIdx.x * PT + threadIdx.x; f < nf; f += (long)gridDim.x * PT) {
-    const int64_t* t = faces + 3 * f;
-    const int ok = in_range(t, n);
+    const int64_t* t = faces + NV * f;
+    const int ok = in_range<NV>(t, n);
     fok[f] = ok;
     if (ok)
-      for (int v = 0; v < 3; ++v) atomicAdd(&cnt[(int)t[v]], 1);
+      for (int v = 0; v < NV; ++v) atomicAdd(&cnt[(int)t[v]], 1);
     else
       bad = 1;
   }
   if (bad) atomicOr(status, AR_RANGE);
 }
 
-// Item i = 3 f + v: face f under its vertex faces[f][v], ordered by face (then by v: a face that names a node
+// Item i = NV f + v: face f under its vertex faces[f][v], ordered by face (then by v: a face that names a node
 // twice gives it two terms, as the host's add.at over faces.ravel() does).
+template <int NV>
 struct FaceByNode {
   const int64_t* faces;
   const int* fok;
   u64* sorted;
   __device__ bool item(long i, int& major, unsigned& minor) const {
-    const long f = i / 3;
+    const long f = i / NV;
     if (!fok[f]) return false;
     major = (int)faces[i];
     minor = (unsigned)f;
@@ -472,8 +518,12 @@ struct FaceByNode {
   __device__ void emit(long k, int, u64 slot) const { sorted[k] = slot; }
 };
 
-// Row r: the sum of its faces' area / 3 in fp64, in face order, rounded once; a node of no face gets exactly 0.
+// Row r: the sum of its faces' shares in fp64, in face order, rounded once; a node of no face gets exactly 0.  A
+// triangle's share is area / 3.  A quad's share at its corner k is the integral of the bilinear N_k over it,
+// (|det| + sgn(det) t_k) / 12 with t_k = (p[k+1] - p[k]) x (p[k-1] - p[k]), twice the signed corner triangle
+// (area / 4 on a parallelogram); det == 0 gives 0.
 // Block 0 also writes the bounding box as (xmin, xmax, ymin, ymax).
+template <int NV>
 __global__ __launch_bounds__(PT) void area_emit_kernel(int n, const float* __restrict__ p, int dim,
                                                        const int64_t* __restrict__ faces,
                                                        const int* __restrict__ rowptr, const u64* __restrict__ sorted,
@@ -495,7 +545,18 @@ __global__ __launch_bounds__(PT) void area_emit_kernel(int n, const float* __res
     double a = 0.0;
     for (int k = b; k < e; ++k) {
       const unsigned f = (unsigned)(sorted[k] >> 32);
-      a += 0.5 * fabs(triangle(p, dim, faces + 3 * (size_t)f).det) / 3.0;
+      const Cell<NV> t = cell<NV>(p, dim, faces + NV * (size_t)f);
+      if constexpr (NV == 3) {
+        a += 0.5 * fabs(t.det) / 3.0;
+      } else {
+        const unsigned v = (unsigned)(sorted[k] & 0xffffffffu) - NV * f;   // the corner: item position - NV f
+        const unsigned nx = next_of<NV>(v), pv = prev_of<NV>(v);
+        const double xk = pick<NV>(t.x, v), yk = pick<NV>(t.y, v);
+        const double e0 = (pick<NV>(t.x, nx) - xk) * (pick<NV>(t.y, pv) - yk);
+        const double e1 = (pick<NV>(t.y, nx) - yk) * (pick<NV>(t.x, pv) - xk);
+        const double tk = e0 - e1;
+        a += t.det == 0.0 ? 0.0 : (fabs(t.det) + (t.det > 0.0 ? tk : -tk)) / 12.0;
+      }
     }
     area[r] = (float)a;
   }
@@ -536,9 +597,11 @@ struct EndByNode {
   __device__ void emit(long k, int, u64 slot) const { sorted2[k] = slot; }
 };
 
-// Node r: its boundary edges in ascending order of the other endpoint.  Edge (a, b) of face (a, b, c), in the
-// face's own order: r = (yb - ya, -(xb - xa)), negated when r . (pc - pa) > 0 so that it points away from c;
-// bvec = 1/2 sum r, blen = 1/2 sum |r|, fp64 sums rounded once.  A node of no boundary edge gets exact zeros.
+// Node r: its boundary edges in ascending order of the other endpoint.  Edge (a, b) of face (a, b, c[, d]), in the
+// face's own order (c: the vertex after b): r = (yb - ya, -(xb - xa)), negated when r . (pc - pa) > 0 so that it
+// points away from c; bvec = 1/2 sum r, blen = 1/2 sum |r|, fp64 sums rounded once.  A node of no boundary edge gets
+// exact zeros.
+template <int NV>
 __global__ __launch_bounds__(PT) void bvec_emit_kernel(int n, const float* __restrict__ p, int dim,
                                                        const int64_t* __restrict__ faces,
                                                        const int* __restrict__ rowptr2,
@@ -554,15 +617,15 @@ __global__ __launch_bounds__(PT) void bvec_emit_kernel(int n, const float* __res
     for (int q = b; q < e; ++q) {
       const unsigned k = (unsigned)(sorted2[q] & 0xffffffffu) >> 1;
       const unsigned pos = (unsigned)(sorted[k] & 0xffffffffu);
-      const unsigned f = pos / 3, j = pos - 3 * f;
-      const int64_t* t = faces + 3 * (size_t)f;
-      const size_t ia = (size_t)t[j], ib = (size_t)t[j == 2 ? 0 : j + 1], ic = (size_t)t[j == 0 ? 2 : j - 1];
+      const unsigned f = pos / NV, j = pos - NV * f;
+      const int64_t* t = faces + NV * (size_t)f;
+      const size_t ia = (size_t)t[j], ib = (size_t)t[next_of<NV>(j)], ic = (size_t)t[next_of<NV>(next_of<NV>(j))];
       const double xa = p[ia * dim], ya = p[ia * dim + 1];
       const double xb = p[ib * dim], yb = p[ib * dim + 1];
       const double xc = p[ic * dim], yc = p[ic * dim + 1];
       double rx = yb - ya, ry = -(xb - xa);
       sl += sqrt(rx * rx + ry * ry);
-      if (triangle(p, dim, t).det == 0.0) {
+      if (cell<NV>(p, dim, t).det == 0.0) {
         bad |= BV_FLAT;
         continue;
       }
@@ -580,25 +643,13 @@ __global__ __launch_bounds__(PT) void bvec_emit_kernel(int n, const float* __res
   if (bad) atomicOr(status, bad);
 }
 
-}  // namespace
 
-extern "C" long pdg_mesh_fields_scratch_bytes(int n_nodes, int n_faces) {
-  if (!sizes_ok(n_nodes, n_faces)) return -1;
-  return (long)std::max(label_layout(n_nodes, n_faces, nullptr, nullptr),
-                        div_layout(n_nodes, n_faces, nullptr, nullptr));
-}
-
-extern "C" int pdg_node_labels(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
-                               int64_t* labels, int* info, void* scratch, long scratch_bytes, void* stream) {
-  PDG_CHECK_ARG(sizes_ok(n_nodes, n_faces) && (dim == 2 || dim == 3),
-                "pdg_node_labels: bad sizes (n_nodes > 0, n_faces >= 0, dim 2 or 3, n_nodes + 1024 and "
-                "9 n_faces + 1024 < 2^31)");
-  PDG_CHECK_ARG(points && labels && info && scratch && (faces || n_faces == 0), "pdg_node_labels: null argument");
-  PDG_CHECK_ARG(scratch_bytes >= pdg_mesh_fields_scratch_bytes(n_nodes, n_faces),
-                "pdg_node_labels: scratch too small");
-  hipStream_t st = (hipStream_t)stream;
+// ------------------------------------------------------------------------------------ launchers
+template <int NV>
+void labels_launch(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces, int64_t* labels,
+                   int* info, void* scratch, hipStream_t st) {
   LabelScratch s;
-  label_layout(n_nodes, n_faces, &s, (char*)scratch);
+  label_layout(n_nodes, n_faces, NV, &s, (char*)scratch);
   const long n = n_nodes;
   int* cnt = s.zero;             // [n + 1]
   int* fill = cnt + n + 1;       // [n]
@@ -610,9 +661,9 @@ extern "C" int pdg_node_labels(int n_nodes, const float* points, int dim, int n_
   hipLaunchKernelGGL(clear_kernel, dim3(grid_for(5 * n + 2)), dim3(PT), 0, st, s.zero, 5 * n + 2, info, 3L,
                      (int*)nullptr, 0L, (int*)nullptr);
   if (n_faces > 0)
-    hipLaunchKernelGGL(label_face_kernel, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok, cnt,
-                       info + 2);
-  group(EdgeByMin{faces, s.fok, s.sorted}, 3L * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
+    hipLaunchKernelGGL(label_face_kernel<NV>, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok,
+                       cnt, info + 2);
+  group(EdgeByMin<NV>{faces, s.fok, s.sorted}, (long)NV * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
   hipLaunchKernelGGL(boundary_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, cnt, s.sorted, 0, bdeg, bcnt, s.lab,
                      (const int*)nullptr, (int*)nullptr, (int*)nullptr);
   scan(n_nodes, bcnt, s.bsum, st);
@@ -622,24 +673,13 @@ extern "C" int pdg_node_labels(int n_nodes, const float* points, int dim, int n_
   hipLaunchKernelGGL(external_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, s.bbox, nbb, bdeg,
                      s.lab, ext, info);
   hipLaunchKernelGGL(labels_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, bdeg, s.lab, ext, labels, info);
-  PDG_CHECK_LAUNCH("pdg_node_labels");
-  return PDG_OK;
 }
 
-extern "C" int pdg_p1_div_operator(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
-                                   int64_t* rows, int64_t* cols, float* vals, long capacity, int* nnz, int* status,
-                                   void* scratch, long scratch_bytes, void* stream) {
-  PDG_CHECK_ARG(sizes_ok(n_nodes, n_faces) && (dim == 2 || dim == 3),
-                "pdg_p1_div_operator: bad sizes (n_nodes > 0, n_faces >= 0, dim 2 or 3, n_nodes + 1024 and "
-                "9 n_faces + 1024 < 2^31)");
-  PDG_CHECK_ARG(points && nnz && status && scratch && (faces || n_faces == 0), "pdg_p1_div_operator: null argument");
-  PDG_CHECK_ARG(n_faces == 0 || (rows && cols && vals), "pdg_p1_div_operator: null argument");
-  PDG_CHECK_ARG(scratch_bytes >= pdg_mesh_fields_scratch_bytes(n_nodes, n_faces),
-                "pdg_p1_div_operator: scratch too small");
-  PDG_CHECK_ARG(capacity >= 18L * n_faces, "pdg_p1_div_operator: capacity below 18 * faces");
-  hipStream_t st = (hipStream_t)stream;
+template <int NV>
+void div_launch(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces, int64_t* rows,
+                int64_t* cols, float* vals, int* nnz, int* status, void* scratch, hipStream_t st) {
   DivScratch s;
-  div_layout(n_nodes, n_faces, &s, (char*)scratch);
+  div_layout(n_nodes, n_faces, NV, &s, (char*)scratch);
   const long n = n_nodes;
   int* cnt = s.zero;             // [n + 1]
   int* fill = cnt + n + 1;       // [n]
@@ -647,30 +687,20 @@ extern "C" int pdg_p1_div_operator(int n_nodes, const float* points, int dim, in
   hipLaunchKernelGGL(clear_kernel, dim3(grid_for(3 * n + 2)), dim3(PT), 0, st, s.zero, 3 * n + 2, nnz, 1L,
                      (int*)nullptr, 0L, status);
   if (n_faces > 0)
-    hipLaunchKernelGGL(div_face_kernel, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, points, dim,
-                       s.fok, cnt, status);
-  group(PairByRow{faces, s.fok, s.sorted}, 9L * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
+    hipLaunchKernelGGL(div_face_kernel<NV>, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, points,
+                       dim, s.fok, cnt, status);
+  group(PairByRow<NV>{faces, s.fok, s.sorted}, (long)(NV * NV) * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
   hipLaunchKernelGGL(div_count_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, cnt, s.sorted, ucnt);
   scan(n_nodes, ucnt, s.bsum, st);
-  hipLaunchKernelGGL(div_emit_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt, s.sorted,
-                     ucnt, rows, cols, vals, nnz);
-  PDG_CHECK_LAUNCH("pdg_p1_div_operator");
-  return PDG_OK;
+  hipLaunchKernelGGL(div_emit_kernel<NV>, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt,
+                     s.sorted, ucnt, rows, cols, vals, nnz);
 }
 
-extern "C" int pdg_nodal_areas(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
-                               float* area, float* bbox, int* status, void* scratch, long scratch_bytes,
-                               void* stream) {
-  PDG_CHECK_ARG(sizes_ok(n_nodes, n_faces) && (dim == 2 || dim == 3),
-                "pdg_nodal_areas: bad sizes (n_nodes > 0, n_faces >= 0, dim 2 or 3, n_nodes + 1024 and "
-                "9 n_faces + 1024 < 2^31)");
-  PDG_CHECK_ARG(points && area && bbox && status && scratch && (faces || n_faces == 0),
-                "pdg_nodal_areas: null argument");
-  PDG_CHECK_ARG(scratch_bytes >= pdg_mesh_fields_scratch_bytes(n_nodes, n_faces),
-                "pdg_nodal_areas: scratch too small");
-  hipStream_t st = (hipStream_t)stream;
-  LabelScratch s;   // the labels' layout holds all that is needed here: bbox, cnt | fill, bsum, fok, 3 F slots twice
-  label_layout(n_nodes, n_faces, &s, (char*)scratch);
+template <int NV>
+void areas_launch(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces, float* area,
+                  float* bbox, int* status, void* scratch, hipStream_t st) {
+  LabelScratch s;   // the labels' layout holds all that is needed here: bbox, cnt | fill, bsum, fok, NV F slots twice
+  label_layout(n_nodes, n_faces, NV, &s, (char*)scratch);
   const long n = n_nodes;
   int* cnt = s.zero;             // [n + 1]
   int* fill = cnt + n + 1;       // [n]
@@ -679,33 +709,18 @@ extern "C" int pdg_nodal_areas(int n_nodes, const float* points, int dim, int n_
   hipLaunchKernelGGL(clear_kernel, dim3(grid_for(2 * n + 1)), dim3(PT), 0, st, s.zero, 2 * n + 1, (int*)nullptr, 0L,
                      (int*)nullptr, 0L, status);
   if (n_faces > 0)
-    hipLaunchKernelGGL(area_face_kernel, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok, cnt,
-                       status);
-  group(FaceByNode{faces, s.fok, s.sorted}, 3L * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
-  hipLaunchKernelGGL(area_emit_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt, s.sorted,
-                     s.bbox, nbb, area, bbox);
-  PDG_CHECK_LAUNCH("pdg_nodal_areas");
-  return PDG_OK;
+    hipLaunchKernelGGL(area_face_kernel<NV>, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok,
+                       cnt, status);
+  group(FaceByNode<NV>{faces, s.fok, s.sorted}, (long)NV * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
+  hipLaunchKernelGGL(area_emit_kernel<NV>, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt,
+                     s.sorted, s.bbox, nbb, area, bbox);
 }
 
-extern "C" long pdg_boundary_vectors_scratch_bytes(int n_nodes, int n_faces) {
-  if (!sizes_ok(n_nodes, n_faces)) return -1;
-  return (long)bvec_layout(n_nodes, n_faces, nullptr, nullptr);
-}
-
-extern "C" int pdg_boundary_vectors(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
-                                    float* bvec, float* blen, int* status, void* scratch, long scratch_bytes,
-                                    void* stream) {
-  PDG_CHECK_ARG(sizes_ok(n_nodes, n_faces) && (dim == 2 || dim == 3),
-                "pdg_boundary_vectors: bad sizes (n_nodes > 0, n_faces >= 0, dim 2 or 3, n_nodes + 1024 and "
-                "9 n_faces + 1024 < 2^31)");
-  PDG_CHECK_ARG(points && bvec && blen && status && scratch && (faces || n_faces == 0),
-                "pdg_boundary_vectors: null argument");
-  PDG_CHECK_ARG(scratch_bytes >= pdg_boundary_vectors_scratch_bytes(n_nodes, n_faces),
-                "pdg_boundary_vectors: scratch too small");
-  hipStream_t st = (hipStream_t)stream;
+template <int NV>
+void bvec_launch(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces, float* bvec,
+                 float* blen, int* status, void* scratch, hipStream_t st) {
   BvecScratch s;
-  bvec_layout(n_nodes, n_faces, &s, (char*)scratch);
+  bvec_layout(n_nodes, n_faces, NV, &s, (char*)scratch);
   const long n = n_nodes;
   int* cnt = s.zero;             // [n + 1]
   int* fill = cnt + n + 1;       // [n]
@@ -714,13 +729,165 @@ extern "C" int pdg_boundary_vectors(int n_nodes, const float* points, int dim, i
   hipLaunchKernelGGL(clear_kernel, dim3(grid_for(4 * n + 2)), dim3(PT), 0, st, s.zero, 4 * n + 2, (int*)nullptr, 0L,
                      (int*)nullptr, 0L, status);
   if (n_faces > 0)
-    hipLaunchKernelGGL(label_face_kernel, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok, cnt,
-                       status);
-  group(EdgeByMin{faces, s.fok, s.sorted}, 3L * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
+    hipLaunchKernelGGL(label_face_kernel<NV>, dim3(grid_for(n_faces)), dim3(PT), 0, st, n_faces, faces, n_nodes, s.fok,
+                       cnt, status);
+  group(EdgeByMin<NV>{faces, s.fok, s.sorted}, (long)NV * n_faces, n_nodes, cnt, fill, s.bsum, s.slots, st);
   hipLaunchKernelGGL(bvec_mark_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, cnt, s.sorted, s.brow, cnt2);
-  group(EndByNode{cnt, n_nodes, s.brow, s.sorted, s.sorted2}, 6L * n_faces, n_nodes, cnt2, fill2, s.bsum, s.slots, st);
-  hipLaunchKernelGGL(bvec_emit_kernel, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt2, s.sorted2,
-                     s.sorted, bvec, blen, status);
-  PDG_CHECK_LAUNCH("pdg_boundary_vectors");
+  group(EndByNode{cnt, n_nodes, s.brow, s.sorted, s.sorted2}, 2L * NV * n_faces, n_nodes, cnt2, fill2, s.bsum, s.slots,
+        st);
+  hipLaunchKernelGGL(bvec_emit_kernel<NV>, dim3(grid_for(n)), dim3(PT), 0, st, n_nodes, points, dim, faces, cnt2,
+                     s.sorted2, s.sorted, bvec, blen, status);
+}
+
+long fields_bytes(int n_nodes, int n_faces, int nv) {
+  if (!sizes_ok(n_nodes, n_faces, nv)) return -1;
+  return (long)std::max(label_layout(n_nodes, n_faces, nv, nullptr, nullptr),
+                        div_layout(n_nodes, n_faces, nv, nullptr, nullptr));
+}
+
+long bvec_bytes(int n_nodes, int n_faces, int nv) {
+  if (!sizes_ok(n_nodes, n_faces, nv)) return -1;
+  return (long)bvec_layout(n_nodes, n_faces, nv, nullptr, nullptr);
+}
+
+// The host checks every entry point makes before any HIP call, under the entry point's own name (nv == 3 for the
+// triangle entry points).
+#define PDG_CHECK_MESH(name, nv, n_nodes, n_faces, dim)                                                               \
+  do {                                                                                                                \
+    PDG_CHECK_ARG((nv) == 3 || (nv) == 4, "%s: nv must be 3 (triangles) or 4 (quads), got %d", name, (int)(nv));      \
+    PDG_CHECK_ARG(sizes_ok(n_nodes, n_faces, nv) && ((dim) == 2 || (dim) == 3),                                       \
+                  "%s: bad sizes (n_nodes > 0, n_faces >= 0, dim 2 or 3, n_nodes + 1024 and %d n_faces + 1024 < "     \
+                  "2^31)", name, (int)((nv) * (nv)));                                                                 \
+  } while (0)
+
+int labels_run(const char* name, int nv, int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+               int64_t* labels, int* info, void* scratch, long scratch_bytes, void* stream) {
+  PDG_CHECK_MESH(name, nv, n_nodes, n_faces, dim);
+  PDG_CHECK_ARG(points && labels && info && scratch && (faces || n_faces == 0), "%s: null argument", name);
+  PDG_CHECK_ARG(scratch_bytes >= fields_bytes(n_nodes, n_faces, nv), "%s: scratch too small", name);
+  hipStream_t st = (hipStream_t)stream;
+  if (nv == 3)
+    labels_launch<3>(n_nodes, points, dim, n_faces, faces, labels, info, scratch, st);
+  else
+    labels_launch<4>(n_nodes, points, dim, n_faces, faces, labels, info, scratch, st);
+  PDG_CHECK_LAUNCH(name);
   return PDG_OK;
+}
+
+int div_run(const char* name, int nv, int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+            int64_t* rows, int64_t* cols, float* vals, long capacity, int* nnz, int* status, void* scratch,
+            long scratch_bytes, void* stream) {
+  PDG_CHECK_MESH(name, nv, n_nodes, n_faces, dim);
+  PDG_CHECK_ARG(points && nnz && status && scratch && (faces || n_faces == 0), "%s: null argument", name);
+  PDG_CHECK_ARG(n_faces == 0 || (rows && cols && vals), "%s: null argument", name);
+  PDG_CHECK_ARG(scratch_bytes >= fields_bytes(n_nodes, n_faces, nv), "%s: scratch too small", name);
+  PDG_CHECK_ARG(capacity >= 2L * nv * nv * n_faces, "%s: capacity below %d * faces", name, 2 * nv * nv);
+  hipStream_t st = (hipStream_t)stream;
+  if (nv == 3)
+    div_launch<3>(n_nodes, points, dim, n_faces, faces, rows, cols, vals, nnz, status, scratch, st);
+  else
+    div_launch<4>(n_nodes, points, dim, n_faces, faces, rows, cols, vals, nnz, status, scratch, st);
+  PDG_CHECK_LAUNCH(name);
+  return PDG_OK;
+}
+
+int areas_run(const char* name, int nv, int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+              float* area, float* bbox, int* status, void* scratch, long scratch_bytes, void* stream) {
+  PDG_CHECK_MESH(name, nv, n_nodes, n_faces, dim);
+  PDG_CHECK_ARG(points && area && bbox && status && scratch && (faces || n_faces == 0), "%s: null argument", name);
+  PDG_CHECK_ARG(scratch_bytes >= fields_bytes(n_nodes, n_faces, nv), "%s: scratch too small", name);
+  hipStream_t st = (hipStream_t)stream;
+  if (nv == 3)
+    areas_launch<3>(n_nodes, points, dim, n_faces, faces, area, bbox, status, scratch, st);
+  else
+    areas_launch<4>(n_nodes, points, dim, n_faces, faces, area, bbox, status, scratch, st);
+  PDG_CHECK_LAUNCH(name);
+  return PDG_OK;
+}
+
+int bvec_run(const char* name, int nv, int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+             float* bvec, float* blen, int* status, void* scratch, long scratch_bytes, void* stream) {
+  PDG_CHECK_MESH(name, nv, n_nodes, n_faces, dim);
+  PDG_CHECK_ARG(points && bvec && blen && status && scratch && (faces || n_faces == 0), "%s: null argument", name);
+  PDG_CHECK_ARG(scratch_bytes >= bvec_bytes(n_nodes, n_faces, nv), "%s: scratch too small", name);
+  hipStream_t st = (hipStream_t)stream;
+  if (nv == 3)
+    bvec_launch<3>(n_nodes, points, dim, n_faces, faces, bvec, blen, status, scratch, st);
+  else
+    bvec_launch<4>(n_nodes, points, dim, n_faces, faces, bvec, blen, status, scratch, st);
+  PDG_CHECK_LAUNCH(name);
+  return PDG_OK;
+}
+
+}  // namespace
+
+// The triangle entry points: nv == 3 of the same code, with the sizes they always had.
+extern "C" long pdg_mesh_fields_scratch_bytes(int n_nodes, int n_faces) { return fields_bytes(n_nodes, n_faces, 3); }
+
+extern "C" int pdg_node_labels(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                               int64_t* labels, int* info, void* scratch, long scratch_bytes, void* stream) {
+  return labels_run("pdg_node_labels", 3, n_nodes, points, dim, n_faces, faces, labels, info, scratch, scratch_bytes,
+                    stream);
+}
+
+extern "C" int pdg_p1_div_operator(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                                   int64_t* rows, int64_t* cols, float* vals, long capacity, int* nnz, int* status,
+                                   void* scratch, long scratch_bytes, void* stream) {
+  return div_run("pdg_p1_div_operator", 3, n_nodes, points, dim, n_faces, faces, rows, cols, vals, capacity, nnz,
+                 status, scratch, scratch_bytes, stream);
+}
+
+extern "C" int pdg_nodal_areas(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                               float* area, float* bbox, int* status, void* scratch, long scratch_bytes,
+                               void* stream) {
+  return areas_run("pdg_nodal_areas", 3, n_nodes, points, dim, n_faces, faces, area, bbox, status, scratch,
+                   scratch_bytes, stream);
+}
+
+extern "C" long pdg_boundary_vectors_scratch_bytes(int n_nodes, int n_faces) {
+  return bvec_bytes(n_nodes, n_faces, 3);
+}
+
+extern "C" int pdg_boundary_vectors(int n_nodes, const float* points, int dim, int n_faces, const int64_t* faces,
+                                    float* bvec, float* blen, int* status, void* scratch, long scratch_bytes,
+                                    void* stream) {
+  return bvec_run("pdg_boundary_vectors", 3, n_nodes, points, dim, n_faces, faces, bvec, blen, status, scratch,
+                  scratch_bytes, stream);
+}
+
+// The same calls for faces of nv vertices: (n_faces, nv) int64, nv == 3 (bitwise the calls above) or 4.
+extern "C" long pdg_mesh_fields_cells_scratch_bytes(int n_nodes, int n_faces, int nv) {
+  return fields_bytes(n_nodes, n_faces, nv);
+}
+
+extern "C" int pdg_node_labels_cells(int n_nodes, const float* points, int dim, int n_faces, int nv,
+                                     const int64_t* faces, int64_t* labels, int* info, void* scratch,
+                                     long scratch_bytes, void* stream) {
+  return labels_run("pdg_node_labels_cells", nv, n_nodes, points, dim, n_faces, faces, labels, info, scratch,
+                    scratch_bytes, stream);
+}
+
+extern "C" int pdg_div_operator_cells(int n_nodes, const float* points, int dim, int n_faces, int nv,
+                                      const int64_t* faces, int64_t* rows, int64_t* cols, float* vals, long capacity,
+                                      int* nnz, int* status, void* scratch, long scratch_bytes, void* stream) {
+  return div_run("pdg_div_operator_cells", nv, n_nodes, points, dim, n_faces, faces, rows, cols, vals, capacity, nnz,
+                 status, scratch, scratch_bytes, stream);
+}
+
+extern "C" int pdg_nodal_areas_cells(int n_nodes, const float* points, int dim, int n_faces, int nv,
+                                     const int64_t* faces, float* area, float* bbox, int* status, void* scratch,
+                                     long scratch_bytes, void* stream) {
+  return areas_run("pdg_nodal_areas_cells", nv, n_nodes, points, dim, n_faces, faces, area, bbox, status, scratch,
+                   scratch_bytes, stream);
+}
+
+extern "C" long pdg_boundary_vectors_cells_scratch_bytes(int n_nodes, int n_faces, int nv) {
+  return bvec_bytes(n_nodes, n_faces, nv);
+}
+
+extern "C" int pdg_boundary_vectors_cells(int n_nodes, const float* points, int dim, int n_faces, int nv,
+                                          const int64_t* faces, float* bvec, float* blen, int* status, void* scratch,
+                                          long scratch_bytes, void* stream) {
+  return bvec_run("pdg_boundary_vectors_cells", nv, n_nodes, points, dim, n_faces, faces, bvec, blen, status, scratch,
+                  scratch_bytes, stream);
 }

@@ -91,14 +91,14 @@ def load_sample(mesh_filename: str | Path, data_filename: str | Path, periodic_g
     ``pdg.devgraph.mesh_graph`` (the same edges, and bitwise the same lengths
     for single-precision VTK points -- double-precision points are rounded to fp32 first, where
     the reference takes the lengths in fp64 and rounds them: within 1 ulp) and the sample's
-    tensors stay on the host until the caller moves them."""
+    tensors stay on the host until the caller moves them.  A quad mesh (convert_utils.py:63-81) goes
+    through the same builder, under the same statement."""
     points, faces = read_legacy_vtk(mesh_filename)
-    # the device graph builder (pdg_mesh_graph) takes triangles; quad meshes (convert_utils.py:63-81,
-    # not used by the reference's datasets) are built by the host restatement below on any device
-    if device is not None and torch.device(device).type == "cuda" and faces.shape[1] == 3:
+    if device is not None and torch.device(device).type == "cuda" and faces.shape[1] in (3, 4):
         from pdg.devgraph import mesh_graph
         ei, ea = mesh_graph(torch.from_numpy(np.ascontiguousarray(points, np.float32)).to(device),
-                            torch.from_numpy(np.ascontiguousarray(faces, np.int64)).to(device), periodic_graph)
+                            torch.from_numpy(np.ascontiguousarray(faces, np.int64)).to(device), periodic_graph,
+                            cells="any")
         graph = Data(pos=torch.from_numpy(np.ascontiguousarray(points)), edge_index=ei.cpu(), edge_attr=ea.cpu(),
                      face=torch.from_numpy(np.ascontiguousarray(faces.T)))
     else:

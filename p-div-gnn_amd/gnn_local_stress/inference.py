@@ -59,7 +59,8 @@ def predict_and_save(model: models.EncodeProcessDecode, dataloader: DataLoader, 
 
 @torch.no_grad()
 def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic: bool = True,
-                 divergence: bool = False, enforce_mean: str | None = None, boundary: bool = False):
+                 divergence: bool = False, enforce_mean: str | None = None, boundary: bool = False,
+                 cells: str = "triangle"):
     """The reference's published workload (``scripts/benchmark_gnn_fem.py:388-415`` then one
     forward) from a bare mesh: ``mesh`` is a legacy-VTK path or a ``(points, faces)`` pair of
     arrays / tensors, ``mean_stress`` the imposed mean field (3 values).  The graph, the node
@@ -74,7 +75,11 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     ``boundary`` builds the boundary vectors with the graph (``data.boundary_vec``, ``data.boundary_len``)
     and also returns the boundary residuals of the returned prediction
     (``gnn_local_stress.boundary.boundary_residuals``; the periodic columns with ``periodic``), as the last
-    value: ``(data, res)`` or ``(data, div, res)``.  Triangle meshes only."""
+    value: ``(data, res)`` or ``(data, div, res)``.  ``cells`` = ``"triangle"`` (the default: (F, 3) faces only, a
+    quad array is refused), ``"quad"`` ((F, 4) faces) or ``"any"`` (decided by the faces' width, which is what a VTK
+    file's reader returns): a quad mesh gets the four sides of every quad as edges, its labels, the q1 divergence
+    operator, the exact Q1 nodal areas and its boundary vectors from the same device builders
+    (``pdg.devgraph``)."""
     from pdg.devgraph import convert_mesh_to_graph
     from . import boundary as bd, homogenise, losses, vtk_io
     if enforce_mean is not None:
@@ -86,11 +91,11 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     device = next(model.parameters()).device
     points = torch.as_tensor(points).to(device=device, dtype=torch.float32)
     faces = torch.as_tensor(faces).to(device=device, dtype=torch.int64)
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"predict_mesh takes triangle meshes only (faces of shape (F, 3)), got "
-                         f"{tuple(faces.shape)}: quad meshes are not built on the device")
+    if cells == "triangle" and (faces.dim() != 2 or faces.shape[1] != 3):
+        raise ValueError(f"predict_mesh takes triangle meshes only (faces of shape (F, 3)) by default, got "
+                         f"{tuple(faces.shape)}: pass cells='quad' or cells='any' for a quad mesh")
     data = convert_mesh_to_graph(points, faces, mean_stress, None, periodic, divergence,
-                                 areas=enforce_mean is not None, boundary=bool(boundary))
+                                 areas=enforce_mean is not None, boundary=bool(boundary), cells=cells)
     data.local_stress = model.forward(data, scale_output=True, scale_input=True).local_stress
     if enforce_mean is not None:
         data.local_stress = homogenise.enforce_mean(data.local_stress, data, convention=enforce_mean)

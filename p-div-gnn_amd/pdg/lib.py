@@ -133,6 +133,15 @@ SIGNATURES: dict[str, list] = {
     "pdg_mean_correct": [I, P, P, P, P, P, P, P],
     "pdg_boundary_vectors_scratch_bytes": [I, I],
     "pdg_boundary_vectors": [I, P, I, I, P, P, P, P, P, ctypes.c_long, P],
+    # faces of nv vertices (3 or 4): `int nv` follows n_faces
+    "pdg_mesh_graph_cells_scratch_bytes": [I, I, I],
+    "pdg_mesh_graph_cells": [I, P, I, I, I, P, I, P, P, P, ctypes.c_long, P, P, ctypes.c_long, P],
+    "pdg_mesh_fields_cells_scratch_bytes": [I, I, I],
+    "pdg_node_labels_cells": [I, P, I, I, I, P, P, P, P, ctypes.c_long, P],
+    "pdg_div_operator_cells": [I, P, I, I, I, P, P, P, P, ctypes.c_long, P, P, P, ctypes.c_long, P],
+    "pdg_nodal_areas_cells": [I, P, I, I, I, P, P, P, P, P, ctypes.c_long, P],
+    "pdg_boundary_vectors_cells_scratch_bytes": [I, I, I],
+    "pdg_boundary_vectors_cells": [I, P, I, I, I, P, P, P, P, P, ctypes.c_long, P],
     "pdg_boundary_residuals": [I] + [P] * 12,
     "pdg_boundary_residuals_bwd": [I] + [P] * 14,
 }
@@ -141,6 +150,8 @@ SIGNATURES: dict[str, list] = {
 _RESTYPES = {"pdg_last_error": ctypes.c_char_p, "pdg_source_hash": ctypes.c_char_p,
              "pdg_mesh_graph_scratch_bytes": ctypes.c_long, "pdg_graph_plan_scratch_bytes": ctypes.c_long,
              "pdg_mesh_fields_scratch_bytes": ctypes.c_long, "pdg_boundary_vectors_scratch_bytes": ctypes.c_long,
+             "pdg_mesh_graph_cells_scratch_bytes": ctypes.c_long, "pdg_mesh_fields_cells_scratch_bytes": ctypes.c_long,
+             "pdg_boundary_vectors_cells_scratch_bytes": ctypes.c_long,
              "pdg_version": c_int, "pdg_max_blocks": c_int, "pdg_wgrad_slabs_per_cu": c_int, "pdg_pq_layout": c_int}
 
 LN_STAT_BYTES = 40   # sizeof(pdg_ln_stat)

@@ -38,7 +38,7 @@ NODE_EXTERNAL_BOUNDARY = 1
 @dataclass
 class MeshSample:
     pos: np.ndarray            # (N, 2) float32
-    faces: np.ndarray          # (F, 3) int64
+    faces: np.ndarray          # (F, 3) int64; (F, 4) from quad_hole_plate
     node_types: np.ndarray     # (N,) int64
     edge_index: np.ndarray     # (2, E) int64, coalesced (sorted by (src, dst))
     edge_attr: np.ndarray      # (E,) float32
@@ -69,6 +69,35 @@ def _grid_triangles(n: int) -> np.ndarray:
     t1 = np.where(even[:, None], np.stack([p00, p10, p11], 1), np.stack([p00, p10, p01], 1))
     t2 = np.where(even[:, None], np.stack([p00, p11, p01], 1), np.stack([p10, p11, p01], 1))
     return np.concatenate([t1, t2], 0).astype(np.int64)
+
+
+def _grid_quads(n: int) -> np.ndarray:
+    """The (n - 1)^2 cells of the n x n grid as counter-clockwise quads, in _grid_triangles' cell order."""
+    i, j = np.meshgrid(np.arange(n - 1), np.arange(n - 1), indexing="xy")
+    p00 = (j * n + i).ravel()
+    return np.stack([p00, p00 + 1, p00 + n + 1, p00 + n], 1).astype(np.int64)
+
+
+def _cells(faces) -> np.ndarray:
+    """``faces`` as (F, 3) or (F, 4) int64: an (F, 4) array is a quad mesh, anything else is read as triangles."""
+    faces = np.asarray(faces, dtype=np.int64)
+    return faces if faces.ndim == 2 and faces.shape[1] == 4 else faces.reshape(-1, 3)
+
+
+def _sides(faces: np.ndarray) -> np.ndarray:
+    """The sides (v_j, v_j+1), cyclic, of every face, side by side: (nv F, 2).  Never a quad's diagonal."""
+    nv = faces.shape[1]
+    return np.concatenate([faces[:, [j, (j + 1) % nv]] for j in range(nv)], 0)
+
+
+def _det(p: np.ndarray, t) -> float:
+    """2 x the signed area of the face with vertices ``t`` (fp64 rows of ``p``): ``p1_divergence_operator``'s
+    det of a triangle, ``q1_divergence_operator``'s of a quad."""
+    if len(t) == 4:
+        (xa, ya), (xb, yb), (xc, yc), (xd, yd) = (p[v, :2] for v in t)
+        return (xc - xa) * (yd - yb) - (xd - xb) * (yc - ya)
+    (xa, ya), (xb, yb), (xc, yc) = (p[v, :2] for v in t)
+    return (xb - xa) * (yc - ya) - (xc - xa) * (yb - ya)
 
 
 def coalesce(edge_index: np.ndarray, edge_attr: np.ndarray | None, num_nodes: int):
@@ -171,17 +200,94 @@ def p1_divergence_operator(pos: np.ndarray, faces: np.ndarray):
     return (uniq // (2 * n)).astype(np.int64), (uniq % (2 * n)).astype(np.int64), acc.astype(np.float32)
 
 
+def q1_divergence_operator(pos: np.ndarray, faces: np.ndarray):
+    """The quad counterpart of ``p1_divergence_operator`` (a function of its own; that one is unchanged): the same
+    area-averaged construction with the element's mean Q1 gradient.  For the quad (a, b, c, d) in its own vertex
+    order, ``det = (xc - xa)(yd - yb) - (xd - xb)(yc - ya)`` (the diagonals' cross product, 2 x the signed area),
+    ``area = |det| / 2``, ``gx = [yb - yd, yc - ya, yd - yb, ya - yc] / det`` and
+    ``gy = [xd - xb, xa - xc, xb - xd, xc - xa] / det``: ``area * g[vn]`` is exactly the integral of grad N_vn over
+    the face for the bilinear shape functions of any quad, and the formula reduces to the P1 one on a triangle.
+    Row i (each of the 4 vertices) receives ``area * gx[vn]`` at column vn and ``area * gy[vn]`` at column vn + N,
+    divided by the node's summed incident area; entries are summed per (row, col) in face order, sorted by key,
+    structural zeros kept (32 items per face).  fp64 from the float32 coordinates, each expression as written
+    here, rounded once.  ``det == 0`` divides by zero, as in the P1 function.  The host restatement of
+    ``pdg_div_operator_cells`` with nv = 4 (csrc/pdg_meshfields.hip)."""
+    n = len(pos)
+    p = np.asarray(pos, dtype=np.float32).astype(np.float64)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 4)
+    a, b, c, d = faces[:, 0], faces[:, 1], faces[:, 2], faces[:, 3]
+    xa, ya = p[a, 0], p[a, 1]
+    xb, yb = p[b, 0], p[b, 1]
+    xc, yc = p[c, 0], p[c, 1]
+    xd, yd = p[d, 0], p[d, 1]
+    det = (xc - xa) * (yd - yb) - (xd - xb) * (yc - ya)  # 2 * signed area
+    area = 0.5 * np.abs(det)
+    gx = np.stack([yb - yd, yc - ya, yd - yb, ya - yc], 1) / det[:, None]
+    gy = np.stack([xd - xb, xa - xc, xb - xd, xc - xa], 1) / det[:, None]
+    rows, cols, vals = [], [], []
+    wsum = np.zeros(n)
+    np.add.at(wsum, faces.ravel(), np.repeat(area, 4))
+    for vi in range(4):
+        i = faces[:, vi]
+        for vn in range(4):
+            nn = faces[:, vn]
+            rows += [i, i]
+            cols += [nn, nn + n]
+            vals += [area * gx[:, vn], area * gy[:, vn]]
+    rows = np.concatenate(rows)
+    cols = np.concatenate(cols)
+    vals = np.concatenate(vals) / wsum[rows]
+    key = rows * (2 * n) + cols
+    uniq, inv = np.unique(key, return_inverse=True)
+    acc = np.zeros(len(uniq))
+    np.add.at(acc, inv, vals)
+    return (uniq // (2 * n)).astype(np.int64), (uniq % (2 * n)).astype(np.int64), acc.astype(np.float32)
+
+
+def cell_divergence_operator(pos: np.ndarray, faces: np.ndarray):
+    """``q1_divergence_operator`` for an (F, 4) array, ``p1_divergence_operator`` otherwise."""
+    faces = np.asarray(faces)
+    quad = faces.ndim == 2 and faces.shape[1] == 4
+    return q1_divergence_operator(pos, faces) if quad else p1_divergence_operator(pos, faces)
+
+
+def _quad_nodal_areas(p: np.ndarray, faces: np.ndarray) -> np.ndarray:
+    """fp64 nodal sums of the exact Q1 integrals: corner k of the quad receives
+    ``(|det| + sgn(det) t_k) / 12`` with ``t_k = (x[k+1] - x[k])(y[k-1] - y[k]) - (y[k+1] - y[k])(x[k-1] - x[k])``
+    (k - 1, k + 1 cyclic: twice the signed corner triangle) and ``q1_divergence_operator``'s det."""
+    x, y = p[faces, 0], p[faces, 1]                      # (F, 4)
+    det = (x[:, 2] - x[:, 0]) * (y[:, 3] - y[:, 1]) - (x[:, 3] - x[:, 1]) * (y[:, 2] - y[:, 0])
+    terms = np.empty(faces.shape)
+    for k in range(4):
+        nx, pv = (k + 1) % 4, (k + 3) % 4
+        tk = (x[:, nx] - x[:, k]) * (y[:, pv] - y[:, k]) - (y[:, nx] - y[:, k]) * (x[:, pv] - x[:, k])
+        terms[:, k] = (np.abs(det) + np.sign(det) * tk) / 12.0
+    acc = np.zeros(len(p))
+    np.add.at(acc, faces.ravel(), terms.ravel())
+    return acc
+
+
 def nodal_areas(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
-    """Lumped nodal areas of a triangle mesh: (area (N,) float32, bbox (4,) float32 = xmin, xmax, ymin, ymax).
+    """Lumped nodal areas of a triangle mesh (an (F, 4) ``faces`` is a quad mesh, see the end; the triangle result
+    is unchanged): (area (N,) float32, bbox (4,) float32 = xmin, xmax, ymin, ymax).
     ``area[n]`` is the sum of ``area_f / 3`` over the faces that hold n: for P1 triangles exactly the reference's
     quadrature weights gathered to the nodes, so ``area / cell area`` is its ``op_mean_stress``
     (``scripts/generate_dataset.py:73-82``) and ``sum(area * field)`` its ``integrate_field``.  fp64 from the
     float32 coordinates with the ``det`` of ``p1_divergence_operator``, a node's terms added in face order and
     rounded once; a node of no face gets 0.  The host restatement of ``pdg_nodal_areas``
-    (csrc/pdg_meshfields.hip)."""
+    (csrc/pdg_meshfields.hip).
+
+    Quads: ``area[n]`` is the sum over the faces of the integral of the bilinear N_n, exactly
+    ``(|det| + sgn(det) t_k) / 12`` at the face's corner k (``_quad_nodal_areas``): ``area_f / 4`` on a
+    parallelogram, and what a 2 x 2 Gauss rule gathers to the nodes, i.e. the reference's ``op_mean_stress``
+    weights for quads.  A face of zero area (``det == 0``) adds 0.  The restatement of ``pdg_nodal_areas_cells``
+    with nv = 4."""
     p32 = np.asarray(pos, dtype=np.float32)
-    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    faces = _cells(faces)
     p = p32.astype(np.float64)
+    if faces.shape[1] == 4:
+        bbox = np.array([p32[:, 0].min(), p32[:, 0].max(), p32[:, 1].min(), p32[:, 1].max()], np.float32)
+        return _quad_nodal_areas(p, faces).astype(np.float32), bbox
     a, b, c = faces[:, 0], faces[:, 1], faces[:, 2]
     xa, ya = p[a, 0], p[a, 1]
     xb, yb = p[b, 0], p[b, 1]
@@ -195,7 +301,9 @@ def nodal_areas(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np.ndar
 
 
 def boundary_vectors(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
-    """Lumped outward boundary vectors of a triangle mesh: (bvec (N, 2) float32, blen (N,) float32).  A boundary
+    """Lumped outward boundary vectors of a triangle mesh, or of a quad mesh when ``faces`` is (F, 4) (the same
+    function: a quad's side (v_j, v_j+1) takes v_j+2 as its third vertex c and the quad's det; the triangle
+    result is unchanged): (bvec (N, 2) float32, blen (N,) float32).  A boundary
     edge belongs to exactly one face (``node_labels``' definition).  For the boundary edge (a, b) of face
     (a, b, c), in the face's own vertex order, ``r = (yb - ya, -(xb - xa))`` in fp64 from the float32
     coordinates, negated if ``r . (pc - pa) > 0``: it then points out of the material, away from the third
@@ -206,13 +314,14 @@ def boundary_vectors(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np
     force (the lumped traction integral), so ``sum bvec`` over a closed boundary is 0.  The host restatement of
     ``pdg_boundary_vectors`` (csrc/pdg_meshfields.hip)."""
     p32 = np.asarray(pos, dtype=np.float32)
-    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    faces = _cells(faces)
+    nv = faces.shape[1]
     p = p32.astype(np.float64)
     n = len(p)
     seen: dict[tuple[int, int], list] = {}
     for f, t in enumerate(faces):
-        for j in range(3):
-            a, b = int(t[j]), int(t[(j + 1) % 3])
+        for j in range(nv):
+            a, b = int(t[j]), int(t[(j + 1) % nv])
             seen.setdefault((min(a, b), max(a, b)), []).append((f, j))
     ends: list[list] = [[] for _ in range(n)]    # per node: (other endpoint, item position, rx, ry, length)
     for (u, v), uses in seen.items():
@@ -220,12 +329,10 @@ def boundary_vectors(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np
             continue
         f, j = uses[0]
         t = faces[f]
-        a, b, c = int(t[j]), int(t[(j + 1) % 3]), int(t[(j + 2) % 3])
+        a, b, c = int(t[j]), int(t[(j + 1) % nv]), int(t[(j + 2) % nv])
         rx, ry = p[b, 1] - p[a, 1], -(p[b, 0] - p[a, 0])
         length = np.sqrt(rx * rx + ry * ry)
-        xa, ya, xb, yb, xc, yc = (*p[t[0], :2], *p[t[1], :2], *p[t[2], :2])
-        det = (xb - xa) * (yc - ya) - (xc - xa) * (yb - ya)
-        if det == 0.0:
+        if _det(p, t) == 0.0:
             rx = ry = 0.0
         elif rx * (p[c, 0] - p[a, 0]) + ry * (p[c, 1] - p[a, 1]) > 0.0:
             rx, ry = -rx, -ry
@@ -244,7 +351,8 @@ def boundary_vectors(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, np
 
 def node_labels(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, int, int]:
     """``compute_node_labels`` (``datasets.py:122-179``) from the mesh alone: (labels (N,) int64,
-    boundary components, external ones).  A boundary edge belongs to exactly one face; the
+    boundary components, external ones).  ``faces`` (F, 3), or (F, 4) for a quad mesh (the same function:
+    a quad's edges are its four sides, never a diagonal).  A boundary edge belongs to exactly one face; the
     boundary nodes (its endpoints) are grouped into connected components over those edges
     (union-find); a component with a node on the bounding box -- x equal to min / max x or y
     equal to min / max y, exactly, in float32 -- is the external boundary (+1), every other one
@@ -252,10 +360,10 @@ def node_labels(pos: np.ndarray, faces: np.ndarray) -> tuple[np.ndarray, int, in
     ``pdg_node_labels`` (csrc/pdg_meshfields.hip); ``hole_plate`` labels its own square plate
     by another rule, so the two check each other."""
     p = np.asarray(pos, dtype=np.float32)
-    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    faces = _cells(faces)
     n = len(p)
     labels = np.zeros(n, np.int64)
-    fe = np.sort(np.concatenate([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]], 0), 1)
+    fe = np.sort(_sides(faces), 1)
     ue, cnt = np.unique(fe, axis=0, return_counts=True) if len(fe) else (fe, np.zeros(0, np.int64))
     be = ue[cnt == 1]
     parent = np.arange(n)
@@ -284,11 +392,28 @@ def hole_plate(n: int = 71, hole_radius: float = 0.0, length: float = 100.0,
                jitter: float = 0.15, periodic: bool = True, seed: int = 69,
                stress_scale: float = 100.0, strain_range: tuple[float, float] | None = None) -> MeshSample:
     """One synthetic sample.  ``hole_radius`` is a fraction of ``length``."""
+    return _plate(_grid_triangles(n), n, hole_radius, length, jitter, periodic, seed, stress_scale, strain_range)
+
+
+def quad_hole_plate(n: int = 71, hole_radius: float = 0.0, jitter: float = 0.15, seed: int = 69,
+                    periodic: bool = True, length: float = 100.0, stress_scale: float = 100.0,
+                    strain_range: tuple[float, float] | None = None) -> MeshSample:
+    """``hole_plate`` with the ``n x n`` grid's cells as quads (``faces`` (F, 4), counter-clockwise), the role of
+    the reference's ``hole_plate_mesh_quad`` (``scripts/generate_dataset_hyperelast.py``): without the quads that
+    have a vertex inside the hole, interior-only jitter (at 0.15 h every quad stays convex), the periodic pairs,
+    the four sides of every quad as edges (``quad_faces_to_edges``), ``q1_divergence_operator`` as ``op_div``, and
+    the labels by the generator's own square-plate rule, so that ``node_labels`` and this check each other."""
+    return _plate(_grid_quads(n), n, hole_radius, length, jitter, periodic, seed, stress_scale, strain_range)
+
+
+def _plate(faces: np.ndarray, n: int, hole_radius: float, length: float, jitter: float, periodic: bool, seed: int,
+           stress_scale: float, strain_range: tuple[float, float] | None) -> MeshSample:
+    """The body of ``hole_plate`` / ``quad_hole_plate``: ``faces`` are the full grid's cells."""
+    quad = faces.shape[1] == 4
     rng = np.random.default_rng(seed)
     h = length / (n - 1)
     gi, gj = np.meshgrid(np.arange(n), np.arange(n), indexing="xy")
     pos = np.stack([gi.ravel() * h, gj.ravel() * h], 1)
-    faces = _grid_triangles(n)
     if hole_radius > 0:
         center = np.array([length / 2, length / 2])
         r = np.linalg.norm(pos - center, axis=1)
@@ -303,7 +428,7 @@ def hole_plate(n: int = 71, hole_radius: float = 0.0, length: float = 100.0,
     num_nodes = len(pos)
 
     # boundary edges (belong to exactly one face)
-    fe = np.sort(np.concatenate([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [0, 2]]], 0), 1)
+    fe = np.sort(_sides(faces), 1)
     ue, cnt = np.unique(fe, axis=0, return_counts=True)
     bnodes = np.unique(ue[cnt == 1].ravel())
     outer = (np.isclose(pos[:, 0], 0) | np.isclose(pos[:, 1], 0)
@@ -316,7 +441,7 @@ def hole_plate(n: int = 71, hole_radius: float = 0.0, length: float = 100.0,
     pos = pos + interior[:, None] * rng.uniform(-jitter * h, jitter * h, size=pos.shape)
     pos = pos.astype(np.float32)
 
-    edge_index = faces_to_edges(faces, num_nodes)
+    edge_index = quad_faces_to_edges(faces, num_nodes) if quad else faces_to_edges(faces, num_nodes)
     edge_attr = edge_lengths(pos, edge_index)
     if periodic:
         pr, pc = periodic_pairs(pos)
@@ -324,7 +449,7 @@ def hole_plate(n: int = 71, hole_radius: float = 0.0, length: float = 100.0,
         ea = np.concatenate([edge_attr, np.zeros(len(pr), np.float32)])
         edge_index, edge_attr = coalesce(ei, ea, num_nodes)
 
-    rows, cols, vals = p1_divergence_operator(pos, faces)
+    rows, cols, vals = cell_divergence_operator(pos, faces)
 
     mean = (rng.uniform(-1.0, 1.0, size=3) * stress_scale).astype(np.float32)
     stiffen = 0.0
