@@ -930,6 +930,68 @@ int pdg_boundary_residuals_bwd(int n_graphs, const int* ptr, const float* sigma,
                                const int* perm, const float* edge_attr, const double* table,
                                const double* g_traction, const double* g_periodic, float* out, void* stream);
 
+/* ---------------------------------------------------------------- fused physics loss (training) */
+/* The hole traction, the periodic jump and the mean-consistency defect as training penalties on the trainer's
+ * STANDARDISED prediction (pdg_physloss.hip), built like the diagnostics above: segmented by ptr[0..B], fp64
+ * arithmetic from the fp32 inputs in a fixed order, kernel launches only (no atomics, no memset, nothing
+ * allocated: every call can be captured).
+ *
+ * y: (N, 3) fp32, the standardised prediction; affine: two fp32 values on the device, (std, mean) of the local
+ * stress.  Every term is evaluated on z = y + mean / std formed in fp64 (= sigma / std: units of the dataset's
+ * standard deviation, dz / dy = 1).  Three argument groups, each given together or all NULL (a NULL group makes
+ * its term absent for every graph, a partial group is refused):
+ *   bvec (N, 2), blen (N), labels (N int64)          as pdg_boundary_residuals takes them,
+ *   rowptr_dst, src, perm, edge_attr                 as pdg_boundary_residuals takes them,
+ *   area (N fp32), target (B, 3 fp32)                the nodal areas of pdg_nodal_areas and each graph's imposed
+ *                                                    mean stress, unstandardised (the kernel forms target / std);
+ *   denom (B fp64) goes with the last group and may be NULL.
+ *
+ * pdg_phys_loss_fwd.  table: (B, 12) fp64 =
+ *   0      L_int, 1 T2, 2 P2, 3 n_pairs   as pdg_boundary_residuals defines them, on z,
+ *   4      W, 5..7 S_xx, S_yy, S_xy       as pdg_graph_wmean defines them, on z with area as weights,
+ *   8      D = denom[g], or W when denom is NULL (the "material" convention); 0 without the mean group,
+ *   9      traction loss T2 / L_int,
+ *   10     periodic loss P2 / n_pairs,
+ *   11     mean loss sum_c (S_c / D - target[g, c] / std)^2.
+ * loss: (B, 3) fp32 = columns 9..11 rounded once.  The training rule, which differs from the diagnostics' NaN
+ * rule on purpose: a term whose denominator is not > 0 is absent for that graph -- its loss is exactly 0 and its
+ * gradient rows are exactly 0 (a plate without a hole, a graph without periodic connections, a graph whose W or D
+ * is not > 0).  A NaN in a participating input still gives a NaN loss, which the step's non-finite test sees.
+ * One 1024-thread workgroup per graph, thread t owning rows t, t + 1024, ... in that order and the block folded
+ * in a fixed order: a graph gets bitwise the same row alone and inside any batch, and from call to call.
+ * n_graphs <= 0, a NULL ptr, y, affine, table or loss, and a partial group are refused on the host before any
+ * launch.
+ *
+ * pdg_phys_loss_bwd.  g_y (N, 3) fp32 receives the gradient with respect to y of
+ *   sum_g scale[0] traction_g + scale[1] periodic_g + scale[2] mean_g,
+ * scale: three fp32 weights on the device (the trainer passes mu / B, as pdg_div_bwd takes penalty / B); table as
+ * the forward wrote it (D is read from it: denom is taken for the group check only).  Per row: the traction and
+ * periodic rows of pdg_boundary_residuals_bwd with g_traction = scale[0], g_periodic = scale[1]; the mean row
+ * 2 area[n] / D (S_c / D - target[g, c] / std) times scale[2] at the rows whose area is > 0.  Each output
+ * element is (float)((double)g_y_old + term) when accumulate is set, else (float)term: one rounding.  A weight
+ * that is exactly 0 switches its term off with exact zeros, whatever the table holds (NaN included); so does a
+ * denominator that is not > 0.  Node-parallel and without atomics.  n_graphs <= 0, n_nodes <= 0, a NULL ptr, y,
+ * affine, table, scale or g_y, and a partial group are refused on the host before any launch.
+ *
+ * pdg_loss_reduce_phys.  pdg_loss_reduce with the three physics sums: out[0..2] as pdg_loss_reduce writes them,
+ * out[4 + k] = scale_phys[k] * sum_g loss_phys[g, k] (fp64 sum in a fixed order, rounded to fp32, scaled in fp32;
+ * exactly 0 when scale_phys[k] is 0 or loss_phys is NULL), out[3] = pdg_loss_reduce's out[3] (bitwise: as its
+ * compiled code forms it, fma(sum_nmse, scale_nmse, out[2])) + out[4] + out[5] + out[6], added in that order in
+ * fp32, so with all three weights 0 the seven values repeat pdg_loss_reduce's four.  loss_phys: (B, 3) fp32 as the forward wrote it; scale_phys: three fp32 values on
+ * the device; both NULL or both given.  out holds 7 values. */
+int pdg_phys_loss_fwd(int n_graphs, const int* ptr, const float* y, const float* affine, const float* bvec,
+                      const float* blen, const int64_t* labels, const int* rowptr_dst, const int* src,
+                      const int* perm, const float* edge_attr, const float* area, const double* denom,
+                      const float* target, double* table, float* loss, void* stream);
+int pdg_phys_loss_bwd(int n_graphs, const int* ptr, int n_nodes, const float* y, const float* affine,
+                      const float* bvec, const float* blen, const int64_t* labels, const int* rowptr_dst,
+                      const int* src, const int* perm, const float* edge_attr, const float* area,
+                      const double* denom, const float* target, const double* table, const float* scale,
+                      int accumulate, float* g_y, void* stream);
+int pdg_loss_reduce_phys(int n_graphs, const float* loss_nmse, const float* loss_div, const float* loss_phys,
+                         float scale_nmse, float scale_div, const float* scale_phys, const float* zero_flag,
+                         float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,14 +85,16 @@ def von_mises_stress(sx, sy, sxy):
 
 
 def load_sample(mesh_filename: str | Path, data_filename: str | Path, periodic_graph: bool = True,
-                device=None) -> Data:
+                device=None, mesh_fields: bool = False) -> Data:
     """One dataset sample exactly as datasets.py:247-281 builds it.  With a HIP ``device`` the
     graph (FaceToEdge, lengths, periodic connections, coalesce) is built there by
     ``pdg.devgraph.mesh_graph`` (the same edges, and bitwise the same lengths
     for single-precision VTK points -- double-precision points are rounded to fp32 first, where
     the reference takes the lengths in fp64 and rounds them: within 1 ulp) and the sample's
     tensors stay on the host until the caller moves them.  A quad mesh (convert_utils.py:63-81) goes
-    through the same builder, under the same statement."""
+    through the same builder, under the same statement.  ``mesh_fields`` (needs a HIP ``device``) also sets
+    ``node_area``, ``cell_area``, ``boundary_vec`` and ``boundary_len`` (``pdg.devgraph.attach_mesh_fields``),
+    what the trainer's physics penalties read."""
     points, faces = read_legacy_vtk(mesh_filename)
     if device is not None and torch.device(device).type == "cuda" and faces.shape[1] in (3, 4):
         from pdg.devgraph import mesh_graph
@@ -117,6 +119,9 @@ def load_sample(mesh_filename: str | Path, data_filename: str | Path, periodic_g
         graph.von_mises = von_mises_stress(msx, msy, msxy)
         graph.surfaces_nodes_for_div = torch.from_numpy(np.asarray(mesh_data["node_labels"], np.int64)).unsqueeze(1)
     graph.nodes_types = graph.surfaces_nodes_for_div
+    if mesh_fields:
+        from pdg.devgraph import attach_mesh_fields
+        attach_mesh_fields(graph, device, cells="any")
     return graph
 
 
@@ -124,10 +129,11 @@ class MeshStressFieldDatasetInMemory:
     """datasets.py:232-311 without PyG: ``len``, indexing, the eight scalar
     standardisation constants of the whole set (:283-291) and the collated data."""
 
-    def __init__(self, dataframe, transform=None, periodic_graph: bool = True, device=None) -> None:
+    def __init__(self, dataframe, transform=None, periodic_graph: bool = True, device=None,
+                 mesh_fields: bool = False) -> None:
         self.dataframe = dataframe
         self.transform = transform
-        self.graphs = [load_sample(m, d, periodic_graph, device)
+        self.graphs = [load_sample(m, d, periodic_graph, device, mesh_fields)
                        for m, d in zip(dataframe["mesh_filename"], dataframe["data_filename"])]
         data = Batch.from_data_list(self.graphs)
         self.mean_pos = data.pos.mean()

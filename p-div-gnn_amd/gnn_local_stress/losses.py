@@ -38,15 +38,79 @@ def _loss(pred, gt, plan: GraphPlan, types, with_nmse: bool, divergence: bool, p
     return total, nmse, div
 
 
+class _PhysicsTerms(torch.autograd.Function):
+    """(traction, periodic, mean) of a standardised prediction, each weight / B times its sum over the graphs:
+    pdg_phys_loss_fwd, and pdg_phys_loss_bwd with the upstream gradients folded into its three weights on the
+    device (csrc/pdg_physloss.hip; no host read either way)."""
+
+    @staticmethod
+    def forward(ctx, pred, affine, weights, ptr, bvec, blen, labels, rowptr, src, perm, ea, area, cell, target):
+        from pdg.lib import lib, ptr as p_, stream_handle
+        B, N = ptr.numel() - 1, pred.shape[0]
+        y = pred.detach().float().contiguous()
+        table = torch.empty(B, 12, dtype=torch.float64, device=y.device)
+        loss = torch.empty(B, 3, dtype=torch.float32, device=y.device)
+        args = (y, affine, bvec, blen, labels, rowptr, src, perm, ea, area, cell, target)
+        lib.pdg_phys_loss_fwd(B, ptr.data_ptr(), *(p_(a) for a in args), table.data_ptr(), loss.data_ptr(),
+                              stream_handle(y.device))
+        ctx.saved = (args, ptr, table, weights, B, N)
+        out = loss.sum(0) * weights
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, g_t, g_p, g_m):
+        from pdg.lib import lib, ptr as p_, stream_handle
+        args, ptr, table, weights, B, N = ctx.saved
+        scale = (torch.stack([g_t, g_p, g_m]).float() * weights).contiguous()
+        g = torch.empty(N, 3, dtype=torch.float32, device=table.device)
+        lib.pdg_phys_loss_bwd(B, ptr.data_ptr(), N, *(p_(a) for a in args), table.data_ptr(), scale.data_ptr(), 0,
+                              g.data_ptr(), stream_handle(g.device))
+        return (g,) + (None,) * 13
+
+
+def _physics_terms(pred, batch, plan: GraphPlan, physics, mean_local_stress, std_local_stress):
+    _check_dev(pred)
+    if mean_local_stress is None or std_local_stress is None:
+        raise ValueError("physics penalties need mean_local_stress and std_local_stress (the terms are evaluated on "
+                         "pred + mean / std)")
+    need = ("boundary_vec", "boundary_len", "node_area") + (("cell_area",) if physics.convention == "cell" else ())
+    missing = [k for k in need if batch.__dict__.get(k) is None]
+    if missing:
+        raise ValueError(f"physics penalties need the batch's {', '.join(missing)}: build the store with "
+                         "DeviceGraphStore(..., mesh_fields=True) (pdg.devgraph.attach_mesh_fields sets them)")
+    dev, f32 = pred.device, torch.float32
+    B = plan.n_graphs
+    affine = torch.stack([torch.as_tensor(std_local_stress, dtype=f32, device=dev).reshape(()),
+                          torch.as_tensor(mean_local_stress, dtype=f32, device=dev).reshape(())])
+    weights = torch.tensor([physics.traction / B, physics.periodic / B, physics.mean / B], dtype=f32, device=dev)
+    cell = batch.cell_area.to(dev, torch.float64).reshape(-1).contiguous() if physics.convention == "cell" else None
+    target = batch.mean_stress.index_select(0, plan.ptr[:-1].long()).float().contiguous()
+    return _PhysicsTerms.apply(
+        pred, affine, weights, plan.ptr, batch.boundary_vec.to(dev, f32).contiguous(),
+        batch.boundary_len.to(dev, f32).reshape(-1).contiguous(),
+        batch.nodes_types.reshape(-1).to(torch.int64).contiguous(), plan.rowptr_dst, plan.src, plan.perm,
+        batch.edge_attr.reshape(-1).float().contiguous(), batch.node_area.to(dev, f32).reshape(-1).contiguous(), cell,
+        target)
+
+
 def batch_loss(pred: torch.Tensor, batch, gt_std: torch.Tensor, divergence: bool = False,
-               divergence_penalty: float = 1.0, reduce_strategy: str = "square"):
-    """Fused gnn_train.py:168-197: returns (total, nmse/B, lambda*div/B)."""
+               divergence_penalty: float = 1.0, reduce_strategy: str = "square", physics=None,
+               mean_local_stress=None, std_local_stress=None):
+    """Fused gnn_train.py:168-197: returns (total, nmse/B, lambda*div/B).  With ``physics`` (a
+    ``pdg.trainer.PhysicsPenalty``) and the local stress's ``mean_local_stress`` / ``std_local_stress`` it returns
+    (total, nmse/B, lambda*div/B, traction, periodic, mean): the boundary and mean-consistency penalties of
+    ``pred`` (standardised) on a batch that carries the mesh fields, each mu / B times its sum over the graphs,
+    and total includes them.  Without ``physics`` the result is what it always was."""
     if reduce_strategy not in ("abs", "square"):
         raise AttributeError("reduce_strategy must be 'abs' or 'square'")
     plan = plan_for(batch)
     types = batch.surfaces_nodes_for_div if batch.surfaces_nodes_for_div is not None else batch.nodes_types
-    return _loss(pred, gt_std, plan, types, True, bool(divergence), float(divergence_penalty),
+    base = _loss(pred, gt_std, plan, types, True, bool(divergence), float(divergence_penalty),
                  reduce_strategy == "abs")
+    if physics is None:
+        return base
+    t, p, m = _physics_terms(pred, batch, plan, physics, mean_local_stress, std_local_stress)
+    return base[0] + t + p + m, base[1], base[2], t, p, m
 
 
 def normalized_mse_loss_single(ground_truth_local_stress: torch.Tensor,

@@ -62,7 +62,7 @@ def make_loaders(train_store: DeviceGraphStore, test_store: DeviceGraphStore, ba
 
 
 def evaluate(model, store: DeviceGraphStore, loader, monitor_divergence: bool, process_group=None,
-             shard: bool = True):
+             shard: bool = True, physics=None):
     """The test pass of gnn_train.py:208-252: sum over batches of (NMSE/B [+ div/B]) and of the
     divergence term (unpenalised, as the reference monitors it), as device scalars.  ``loader``
     yields graph-index lists (an int batch size builds an unshuffled one).
@@ -70,11 +70,16 @@ def evaluate(model, store: DeviceGraphStore, loader, monitor_divergence: bool, p
     With a process group and ``shard`` (replica data parallelism), every rank evaluates its
     ``shard_minibatch`` share of each test minibatch with its losses scaled to / B_global and the
     two sums are all-reduced once at the end; without ``shard`` (dp_mode "sync") every rank
-    evaluates the whole minibatches, so the test loss is the one-device value on every rank."""
+    evaluates the whole minibatches, so the test loss is the one-device value on every rank.
+
+    ``physics`` (a ``pdg.trainer.PhysicsPenalty``; the store must carry the mesh fields): the traction, periodic
+    and mean terms are monitored too, weighted as in training, and a fourth result holds their three sums; the
+    total stays NMSE [+ div], so the checkpoint decision does not depend on the penalties' weights."""
     if isinstance(loader, int):
         loader = index_loader(store.num_graphs, loader, shuffle=False)
     total = torch.zeros((), dtype=torch.float32, device=store.device)
     div_sum = torch.zeros((), dtype=torch.float32, device=store.device)
+    phys_sum = torch.zeros(3, dtype=torch.float32, device=store.device)
     nb = 0
     world = dist.get_world_size(process_group) if process_group is not None else 1
     rank = dist.get_rank(process_group) if process_group is not None else 0
@@ -87,16 +92,28 @@ def evaluate(model, store: DeviceGraphStore, loader, monitor_divergence: bool, p
             batch = store.batch(mine)
             pred = model.forward(batch, scale_output=False, scale_input=True).local_stress
             gt = data_utils.standardize(batch.local_stress, model.mean_local_stress, model.std_local_stress)
-            t, _, d = losses.batch_loss(pred, batch, gt.float().contiguous(), divergence=monitor_divergence,
-                                        divergence_penalty=1.0)
+            if physics is None:
+                t, _, d = losses.batch_loss(pred, batch, gt.float().contiguous(), divergence=monitor_divergence,
+                                            divergence_penalty=1.0)
+            else:
+                full = losses.batch_loss(pred, batch, gt.float().contiguous(), divergence=monitor_divergence,
+                                         divergence_penalty=1.0, physics=physics,
+                                         mean_local_stress=model.mean_local_stress,
+                                         std_local_stress=model.std_local_stress)
+                d = full[2]
+                t = full[1] + d if monitor_divergence else full[1]
             w = len(mine) / len(idx)        # / B_local -> / B_global (1 without sharding)
+            if physics is not None:
+                phys_sum = phys_sum + torch.stack(full[3:]) * w
             total = total + (t * w if w != 1 else t)
             if monitor_divergence:
                 div_sum = div_sum + (d * w if w != 1 else d)
     if world > 1 and shard:
-        sums = torch.stack([total, div_sum])
+        sums = torch.cat([torch.stack([total, div_sum]), phys_sum])
         dist.all_reduce(sums, group=process_group)
-        total, div_sum = sums[0], sums[1]
+        total, div_sum, phys_sum = sums[0], sums[1], sums[2:]
+    if physics is not None:
+        return total, div_sum, nb, phys_sum
     return total, div_sum, nb
 
 
@@ -104,8 +121,11 @@ def train(model: models.EncodeProcessDecode, train_store: DeviceGraphStore, test
           epochs: int, batch_size: int, learning_rate: float = 0.001, weights_folder: str = "",
           early_stopping_limit: int = 10, optimize_divergence: bool = True, divergence_penalty: float = 1.0,
           train_all_epochs: bool = False, monitor_divergence_in_test: bool = False,
-          log=print, loaders=None, process_group=None, dp_mode: str = "replica") -> tuple[list[float], list[float]]:
-    """gnn_train.py:95-305 (without TensorBoard).  ``loaders``: the (train, test) index loaders
+          log=print, loaders=None, process_group=None, dp_mode: str = "replica",
+          physics=None) -> tuple[list[float], list[float]]:
+    """gnn_train.py:95-305 (without TensorBoard).  ``physics`` (a ``pdg.trainer.PhysicsPenalty``; both stores built
+    with ``mesh_fields=True``): the boundary and mean-consistency penalties are trained against and logged beside
+    the NMSE and the divergence, for the train pass and the test pass.  ``loaders``: the (train, test) index loaders
     (make_loaders; built here when omitted).  ``process_group``: graph-batch data parallelism over
     its ranks (module docstring; every rank calls this with the same arguments, rank 0 writes)."""
     train_loader, test_loader = loaders if loaders is not None else make_loaders(train_store, test_store, batch_size)
@@ -114,7 +134,7 @@ def train(model: models.EncodeProcessDecode, train_store: DeviceGraphStore, test
     rank = dist.get_rank(pg) if pg is not None else 0
     writer = rank == 0
     trainer = Trainer(model, lr=learning_rate, divergence=optimize_divergence,
-                      divergence_penalty=divergence_penalty, process_group=pg, dp_mode=dp_mode)
+                      divergence_penalty=divergence_penalty, process_group=pg, dp_mode=dp_mode, physics=physics)
     folder = Path(weights_folder)
     if writer:
         folder.mkdir(parents=True, exist_ok=False)
@@ -137,6 +157,7 @@ def train(model: models.EncodeProcessDecode, train_store: DeviceGraphStore, test
         nmse_sum = torch.zeros((), dtype=torch.float32, device=dev)
         div_sum = torch.zeros((), dtype=torch.float32, device=dev)
         total_sum = torch.zeros((), dtype=torch.float32, device=dev)
+        phys_sum = torch.zeros(3, dtype=torch.float32, device=dev)
         n_train = 0
         for idx in train_loader:
             if world == 1:
@@ -153,12 +174,17 @@ def train(model: models.EncodeProcessDecode, train_store: DeviceGraphStore, test
             total_sum = total_sum + out["total"]
             if optimize_divergence:
                 div_sum = div_sum + out["div"]
+            if physics is not None:
+                phys_sum = phys_sum + torch.stack([out["traction"], out["periodic"], out["mean"]])
             n_train += 1
         model.eval()
-        test_total, test_div, n_test = evaluate(model, test_store, test_loader, monitor_divergence_in_test,
-                                                process_group=pg, shard=dp_mode == "replica")
+        test_total, test_div, n_test, *test_phys = evaluate(model, test_store, test_loader, monitor_divergence_in_test,
+                                                            process_group=pg, shard=dp_mode == "replica",
+                                                            physics=physics)
         # one host sync per epoch (the reference's .item() calls, gnn_train.py:258-275)
         vals = torch.stack([nmse_sum, total_sum, div_sum, test_total, test_div]).tolist()
+        if physics is not None:
+            pv = torch.cat([phys_sum / n_train, test_phys[0] / n_test]).tolist()
         train_mse_loss = vals[0] / n_train
         total_loss = vals[1] / n_train
         test_loss = vals[3] / n_test
@@ -176,6 +202,9 @@ def train(model: models.EncodeProcessDecode, train_store: DeviceGraphStore, test
             msg += f"\nDivergence term train {vals[2] / n_train}"
         if monitor_divergence_in_test:
             msg += f"\nDivergence test value {vals[4] / n_test}"
+        if physics is not None:
+            msg += (f"\nTraction / periodic / mean terms train {pv[0]} / {pv[1]} / {pv[2]}"
+                    f"\nTraction / periodic / mean terms test {pv[3]} / {pv[4]} / {pv[5]}")
         log(msg)
         train_losses.append(total_loss)
         test_losses.append(test_loss)
@@ -190,10 +219,15 @@ def run_experience(dataset_train_csv: str, dataset_test_csv: str, results_folder
                    early_stopping_limit: int, learning_rate: float, message_passing_steps: int,
                    train_all_epochs: bool = False, device: str = "cuda", periodic_graph: bool = True,
                    monitor_divergence_in_test: bool = False, config_path: Path = Path(""), *args: Any,
-                   log=print, process_group=None, dp_mode: str = "replica",
+                   log=print, process_group=None, dp_mode: str = "replica", traction_penalty: float = 0.0,
+                   periodic_penalty: float = 0.0, mean_penalty: float = 0.0, mean_convention: str = "cell",
                    **kwargs: Any) -> tuple[list[float], list[float]]:
     """gnn_train.py:331-435.  ``process_group``: graph-batch data parallelism (module docstring);
-    every rank builds the same datasets and loaders, only rank 0 logs and writes."""
+    every rank builds the same datasets and loaders, only rank 0 logs and writes.  ``traction_penalty``,
+    ``periodic_penalty``, ``mean_penalty`` and ``mean_convention`` (optional YAML keys): the weights of the
+    trainer's boundary and mean-consistency penalties (``pdg.trainer.PhysicsPenalty``).  All absent or 0: the run
+    is what it always was.  Otherwise the datasets are loaded with ``mesh_fields=True`` (their graphs then built
+    on the device), the stores carry the mesh fields and the three terms are logged for both passes."""
     import pandas as pd
     if process_group is not None and dist.get_rank(process_group) != 0:
         log = _quiet
@@ -205,12 +239,20 @@ def run_experience(dataset_train_csv: str, dataset_test_csv: str, results_folder
     train_df = pd.read_csv(dataset_train_csv)
     test_df = pd.read_csv(dataset_test_csv)
     log(f"Size train dataset {len(train_df)}\nSize test dataset {len(test_df)}\nLoading datasets...")
-    train_dataset = datasets.MeshStressFieldDatasetInMemory(train_df, periodic_graph=periodic_graph)
+    physics = None
+    extra: dict = {}
+    if traction_penalty or periodic_penalty or mean_penalty:
+        from pdg.trainer import PhysicsPenalty
+        physics = PhysicsPenalty(float(traction_penalty), float(periodic_penalty), float(mean_penalty), mean_convention)
+        extra = dict(device=device, mesh_fields=True)
+        log(f"Traction / periodic / mean penalties {traction_penalty} / {periodic_penalty} / {mean_penalty} "
+            f"({mean_convention} average)")
+    train_dataset = datasets.MeshStressFieldDatasetInMemory(train_df, periodic_graph=periodic_graph, **extra)
     # the reference builds the test set with the default periodic_graph=True (gnn_train.py:386;
     # reproduced, not "fixed")
-    test_dataset = datasets.MeshStressFieldDatasetInMemory(test_df)
-    train_store = DeviceGraphStore(train_dataset.graphs, device)
-    test_store = DeviceGraphStore(test_dataset.graphs, device)
+    test_dataset = datasets.MeshStressFieldDatasetInMemory(test_df, **extra)
+    train_store = DeviceGraphStore(train_dataset.graphs, device, mesh_fields=physics is not None)
+    test_store = DeviceGraphStore(test_dataset.graphs, device, mesh_fields=physics is not None)
     model = models.EncodeProcessDecode(
         input_edges_features_size=1, input_nodes_features_size=6, message_passing_steps=message_passing_steps,
         latent_size=latent_size, output_nodes_features_size=3,
@@ -229,7 +271,7 @@ def run_experience(dataset_train_csv: str, dataset_test_csv: str, results_folder
                  weights_folder=(results / "weights").as_posix(), early_stopping_limit=early_stopping_limit,
                  optimize_divergence=divergence, divergence_penalty=divergence_penalty,
                  train_all_epochs=train_all_epochs, monitor_divergence_in_test=monitor_divergence_in_test,
-                 log=log, loaders=loaders, process_group=process_group, dp_mode=dp_mode)
+                 log=log, loaders=loaders, process_group=process_group, dp_mode=dp_mode, physics=physics)
 
 
 def _quiet(*_a, **_k) -> None:

@@ -34,14 +34,28 @@ assert _JOB.itemsize == 40
 # per-graph arrays kept resident: name -> (source, per-node/edge width, kind)
 _NODE_F32 = (("pos", 2), ("mean_stress", 3), ("local_stress", 3))
 _NODE_I64 = ("nodes_types", "surfaces_nodes_for_div")
+# mesh_fields=True: per-node fp32 arrays (name, width; width 0 = a flat (N,) array) and the per-graph fp64 cell area
+_MESH_F32 = (("node_area", 0), ("boundary_vec", 2), ("boundary_len", 0))
+_MESH_KEYS = tuple(k for k, _ in _MESH_F32) + ("cell_area",)
 
 
 class DeviceGraphStore:
     """A dataset of ``Data`` graphs resident in HBM; ``batch(indices)`` collates on device."""
 
-    def __init__(self, datas: Sequence[Data], device) -> None:
+    def __init__(self, datas: Sequence[Data], device, mesh_fields: bool = False) -> None:
+        """``mesh_fields``: also keep every graph's ``node_area``, ``boundary_vec``, ``boundary_len`` and (fp64)
+        ``cell_area`` resident (``pdg.devgraph.attach_mesh_fields`` sets them) and carry them into every batch,
+        bitwise ``Batch.from_data_list``'s: what the trainer's physics penalties read.  ValueError when a graph
+        lacks one.  Without it a batch is attribute for attribute what it always was."""
         self.device = torch.device(device)
         self.datas = list(datas)
+        self.mesh_fields = bool(mesh_fields)
+        if self.mesh_fields:
+            for i, d in enumerate(self.datas):
+                missing = [k for k in _MESH_KEYS if d.__dict__.get(k) is None]
+                if missing:
+                    raise ValueError(f"mesh_fields=True: graph {i} has no {', '.join(missing)} "
+                                     "(pdg.devgraph.attach_mesh_fields, or load_sample(..., mesh_fields=True))")
         dev = self.device
         G = len(self.datas)
         self.n = np.array([d.num_nodes for d in self.datas], dtype=np.int64)
@@ -74,6 +88,13 @@ class DeviceGraphStore:
             a[k] = flat([d.__dict__[k] for d in self.datas], torch.float32)
         for k in _NODE_I64:
             a[k] = flat([d.__dict__[k] for d in self.datas], torch.int64)
+        if self.mesh_fields:
+            for k, _ in _MESH_F32:
+                a[k] = flat([d.__dict__[k] for d in self.datas], torch.float32)
+            a["cell_area"] = flat([d.__dict__["cell_area"] for d in self.datas], torch.float64)
+            if a["cell_area"].numel() != G or any(a[k].numel() != max(w, 1) * int(self.n.sum()) for k, w in _MESH_F32):
+                raise ValueError("mesh_fields=True: node_area and boundary_len hold one value per node, boundary_vec "
+                                 "two, cell_area one per graph")
         a["edge_attr"] = flat([d.edge_attr for d in self.datas], torch.float32)
         a["ei0"] = flat([d.edge_index[0] for d in self.datas], torch.int64)
         a["ei1"] = flat([d.edge_index[1] for d in self.datas], torch.int64)
@@ -128,6 +149,17 @@ class DeviceGraphStore:
             for j, g in enumerate(idx):
                 job(a[k], int(self.off_n[g]), t, int(bn[j]), int(n[j]), 0, B64)
             setattr(out, k, t)
+        if self.mesh_fields:
+            for k, w in _MESH_F32:
+                ww = max(w, 1)
+                t = torch.empty((N, w) if w else (N,), **f32)
+                for j, g in enumerate(idx):
+                    job(a[k], ww * int(self.off_n[g]), t, ww * int(bn[j]), ww * int(n[j]), 0, F32)
+                setattr(out, k, t)
+            cell = torch.empty(len(idx), dtype=torch.float64, device=dev)
+            for j, g in enumerate(idx):
+                job(a["cell_area"], g, cell, j, 1, 0, B64)     # an 8-byte word plus 0: the fp64 bits as they are
+            out.cell_area = cell
         ea = torch.empty(E, **f32)
         ei = torch.empty(2, E, **i64)
         bvec = torch.empty(N, **i64)

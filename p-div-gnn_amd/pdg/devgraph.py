@@ -249,6 +249,30 @@ def boundary_vectors(points: torch.Tensor, faces: torch.Tensor, cells: str = "tr
     return BoundaryVectors(vec, length)
 
 
+MESH_FIELDS = ("node_area", "cell_area", "boundary_vec", "boundary_len")
+
+
+def attach_mesh_fields(data: Data, device, cells: str = "any") -> Data:
+    """Set ``node_area`` (N,), ``cell_area`` (1,) fp64, ``boundary_vec`` (N, 2) and ``boundary_len`` (N,) on ``data``
+    from its ``pos`` and ``face`` (the (3|4, F) layout of FaceToEdge), computed on the HIP ``device`` by
+    ``nodal_areas`` and ``boundary_vectors`` and kept where ``data.pos`` lives: what ``Batch.from_data_list`` and
+    ``DeviceGraphStore(..., mesh_fields=True)`` carry into a minibatch for the trainer's physics penalties
+    (``pdg.trainer.PhysicsPenalty``).  Returns ``data``."""
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError("attach_mesh_fields computes on a HIP device (the HIP path has no CPU fallback)")
+    pos, face = data.__dict__.get("pos"), data.__dict__.get("face")
+    if pos is None or face is None:
+        raise ValueError("attach_mesh_fields needs the mesh: data.pos (N, 2) and data.face (3|4, F)")
+    pts = pos.to(device).float()
+    fcs = face.to(device).T.contiguous()
+    area = nodal_areas(pts, fcs, cells)
+    bv = boundary_vectors(pts, fcs, cells)
+    home = pos.device
+    data.node_area, data.cell_area = area.area.to(home), area.cell_area.to(home)
+    data.boundary_vec, data.boundary_len = bv.vec.to(home), bv.length.to(home)
+    return data
+
+
 def convert_mesh_to_graph(points: torch.Tensor, faces: torch.Tensor, mean_stress,
                           node_labels: torch.Tensor | None = None, periodic: bool = True,
                           divergence: bool = False, areas: bool = False, boundary: bool = False,

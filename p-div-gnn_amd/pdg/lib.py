@@ -144,6 +144,9 @@ SIGNATURES: dict[str, list] = {
     "pdg_boundary_vectors_cells": [I, P, I, I, I, P, P, P, P, P, ctypes.c_long, P],
     "pdg_boundary_residuals": [I] + [P] * 12,
     "pdg_boundary_residuals_bwd": [I] + [P] * 14,
+    "pdg_phys_loss_fwd": [I] + [P] * 16,
+    "pdg_phys_loss_bwd": [I, P, I] + [P] * 14 + [I, P, P],
+    "pdg_loss_reduce_phys": [I, P, P, P, c_float, c_float, P, P, P, P],
 }
 # the entry points that return a value, not a status: called as they are (no error check, not counted in
 # lib.calls, not passed to lib.hook)

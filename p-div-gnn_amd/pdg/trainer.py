@@ -28,6 +28,16 @@ single kernel.  GradScaler (gnn_train.py:111) is an fp32 power-of-two rescale,
 numerically the identity except that it skips the update when a gradient is
 non-finite; the same skip is applied here.
 
+physics=PhysicsPenalty(...) adds the boundary and mean-consistency penalties to the loss (new in this
+build; the reference's only physics term is the divergence, which zeroes every boundary row): per graph
+the mean-square traction on the hole's edge, the mean-square jump across the periodic connections and the
+squared defect between the prediction's volume average and the imposed mean stress, each in units of the
+dataset's standard deviation and weighted mu / B like the divergence.  Two launches after the divergence's
+(pdg_phys_loss_fwd, then pdg_phys_loss_bwd accumulating into g_y; csrc/pdg_physloss.hip) on the standardised
+output, no host read; the step's scalars come from pdg_loss_reduce_phys and the bucket's tail is 7 wide.
+The batch must carry the mesh fields (DeviceGraphStore(..., mesh_fields=True)).  physics=None is the step as
+it always was, launch for launch.
+
 capture=True records forward, loss and backward of a batch once in a HIP graph
 (torch.cuda.CUDAGraph = hipGraph on ROCm) and replays it on later steps with the
 same batch object: ~250 kernel launches per step become one graph launch.  The
@@ -35,6 +45,8 @@ all-reduce, the non-finite check and Adam stay eager.  Replays run the same kern
 so the results are bit-identical to eager steps (tests/test_gpu_trainer_graph.py).
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import torch
 
@@ -44,12 +56,36 @@ from .lib import lib, stream_handle
 from .plan import plan_for
 
 
+@dataclass(frozen=True)
+class PhysicsPenalty:
+    """Weights of the trainer's boundary and mean-consistency penalties (module docstring): ``traction`` on the
+    hole's mean-square traction, ``periodic`` on the mean-square periodic jump, ``mean`` on the squared defect of
+    the volume average, taken over the cell (``convention="cell"``: S / cell_area, the dataset's mean_stress) or
+    over the material (``"material"``: S / W).  A weight of 0 switches its term off with exact zeros."""
+    traction: float = 0.0
+    periodic: float = 0.0
+    mean: float = 0.0
+    convention: str = "cell"
+
+    def __post_init__(self) -> None:
+        if self.convention not in ("cell", "material"):
+            raise ValueError("convention must be 'cell' or 'material'")
+        if min(self.traction, self.periodic, self.mean) < 0:
+            raise ValueError("a negative penalty weight")
+
+    @property
+    def active(self) -> bool:
+        return bool(self.traction or self.periodic or self.mean)
+
+
 class Trainer:
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  divergence: bool = False, divergence_penalty: float = 1.0, process_group=None,
-                 dp_mode: str = "replica", capture: bool = False) -> None:
+                 dp_mode: str = "replica", capture: bool = False, physics: PhysicsPenalty | None = None) -> None:
         if dp_mode not in ("replica", "sync"):
             raise ValueError("dp_mode must be 'replica' or 'sync'")
+        if physics is not None and not isinstance(physics, PhysicsPenalty):
+            raise TypeError("physics must be a pdg.trainer.PhysicsPenalty or None")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("Trainer needs the model on a HIP device")
@@ -59,6 +95,8 @@ class Trainer:
         self.lr, self.betas, self.eps = lr, betas, eps
         self.divergence = divergence
         self.penalty = float(divergence_penalty)
+        self.physics = physics
+        self._tail = 4 if physics is None else 7     # every rank must agree on it: the bucket is all-reduced
         self.pg = process_group
         self.sync = dp_mode == "sync" and process_group is not None
         sizes = [int(torch.Size(s).numel()) for _, s in PARAM_SHAPES]
@@ -67,8 +105,9 @@ class Trainer:
         # the all-reduced bucket: every parameter gradient, then (pdg_loss_reduce's four scalars) one slot
         # holding 1.0 when this rank's batch has a nonzero mean stress (the zero-mean-stress guard of
         # models.py:294-299, below) and this rank's shares of the global minibatch's NMSE, divergence and
-        # total loss
-        self._bucket = torch.zeros(total + 4, dtype=torch.float32, device=dev)
+        # total loss; with physics penalties (pdg_loss_reduce_phys's seven scalars) also the traction, periodic and
+        # mean terms
+        self._bucket = torch.zeros(total + self._tail, dtype=torch.float32, device=dev)
         self.flat_g = self._bucket[:total]
         self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -96,6 +135,8 @@ class Trainer:
         self._table_key = None
         self._nz_cache: dict = {}
         self._consts: dict = {}
+        self._phys_scales: dict = {}
+        self._affine = None           # (stats8 it was read from, (std, mean) of the local stress on the device)
         # captured forward+backward per batch object (dp_mode="sync" reads counts on the host: eager)
         self.capture = capture and not self.sync
         self._graph = None            # (id(batch), torch.cuda.CUDAGraph, static outputs)
@@ -134,6 +175,47 @@ class Trainer:
         if t is None:
             t = self._consts[v] = torch.full((1,), v, dtype=torch.float32, device=self.device)
         return t
+
+    def _phys_scale(self, Bn: int) -> torch.Tensor:
+        """The three weights mu / B as a (3,) fp32 device tensor, kept like _const's entries."""
+        t = self._phys_scales.get(Bn)
+        if t is None:
+            p = self.physics
+            t = self._phys_scales[Bn] = torch.tensor([p.traction / Bn, p.periodic / Bn, p.mean / Bn],
+                                                     dtype=torch.float32, device=self.device)
+        return t
+
+    def _affine_for(self, stats8: torch.Tensor) -> torch.Tensor:
+        """(std, mean) of the local stress as a (2,) fp32 device tensor, copied on the device from the model's
+        statistics tensor (no host read) when that tensor is a new one.  One tensor for the trainer's lifetime,
+        rewritten in place: a captured HIP graph reads it by address."""
+        if self._affine is None:
+            self._affine = (None, torch.empty(2, dtype=torch.float32, device=self.device))
+        if self._affine[0] is not stats8:
+            a = self._affine[1]
+            a[0:1].copy_(stats8.reshape(-1)[5:6])     # _STAT_ORDER: mean_local_stress at 4, std_local_stress at 5
+            a[1:2].copy_(stats8.reshape(-1)[4:5])
+            self._affine = (stats8, a)
+        return self._affine[1]
+
+    def _phys_inputs(self, batch, N: int, B: int):
+        """The batch's mesh fields as the kernels take them, checked on the host by shape only."""
+        need = ("boundary_vec", "boundary_len", "node_area") + (("cell_area",) if self.physics.convention == "cell" else ())
+        missing = [k for k in need if batch.__dict__.get(k) is None]
+        if missing:
+            raise ValueError(f"physics penalties need the batch's {', '.join(missing)}: build the store with "
+                             "DeviceGraphStore(..., mesh_fields=True) (pdg.devgraph.attach_mesh_fields sets them)")
+        f32 = torch.float32
+        bvec = batch.boundary_vec.to(self.device, f32).contiguous()
+        blen = batch.boundary_len.to(self.device, f32).reshape(-1).contiguous()
+        area = batch.node_area.to(self.device, f32).reshape(-1).contiguous()
+        cell = None
+        if self.physics.convention == "cell":
+            cell = batch.cell_area.to(self.device, torch.float64).reshape(-1).contiguous()
+        if tuple(bvec.shape) != (N, 2) or blen.numel() != N or area.numel() != N or (cell is not None and cell.numel() != B):
+            raise ValueError("mesh fields of the wrong size: boundary_vec (N, 2), boundary_len (N,), node_area (N,), "
+                             "cell_area (B,); build the store with mesh_fields=True")
+        return bvec, blen, area, cell
 
     def _nonzero_flag(self, batch) -> torch.Tensor:
         """1.0 when any mean stress of `batch` is nonzero, else 0.0 (a device scalar): the guard of
@@ -188,6 +270,9 @@ class Trainer:
         plan = plan_for(batch)
         stats8 = m.stats_tensor(self.device)
         B, N = plan.n_graphs, plan.n_nodes
+        if self.physics is not None:
+            self._phys_inputs(batch, N, B)      # a batch without the mesh fields is refused before anything runs
+            self._affine_for(stats8)
         Bn = B                                      # loss normaliser (gnn_train.py:193/196)
         if solo:
             if n_global_graphs is not None and int(n_global_graphs) != B:
@@ -267,6 +352,24 @@ class Trainer:
                             plan.at_comp.data_ptr(), plan.at_val.data_ptr(), div.data_ptr(), sd.data_ptr(), 0, 1,
                             gy.data_ptr(), s)
             out["loss_d"] = loss_d
+        if self.physics is not None:
+            # boundary and mean-consistency penalties on the standardised output: per-graph losses, then their
+            # gradient accumulated into gy (fp64-formed, one rounding per element)
+            bvec, blen, area, cell = self._phys_inputs(batch, N, B)
+            labels = batch.nodes_types.reshape(-1).to(torch.int64).contiguous()
+            # the imposed mean stress: mean_stress is constant over a graph's nodes, its first row is the graph's
+            target = batch.mean_stress.index_select(0, plan.ptr[:-1].long()).float().contiguous()
+            ea = batch.edge_attr.reshape(-1).float().contiguous()
+            ptable = torch.empty(B, 12, dtype=torch.float64, device=self.device)
+            loss_p = torch.empty(B, 3, **f32)
+            affine = self._affine[1]
+            common = (y.data_ptr(), affine.data_ptr(), bvec.data_ptr(), blen.data_ptr(), labels.data_ptr(),
+                      plan.rowptr_dst.data_ptr(), plan.src.data_ptr(), plan.perm.data_ptr(), ea.data_ptr(),
+                      area.data_ptr(), cell.data_ptr() if cell is not None else None, target.data_ptr())
+            lib.pdg_phys_loss_fwd(B, plan.ptr.data_ptr(), *common, ptable.data_ptr(), loss_p.data_ptr(), s)
+            lib.pdg_phys_loss_bwd(B, plan.ptr.data_ptr(), N, *common, ptable.data_ptr(),
+                                  self._phys_scale(Bn).data_ptr(), 1, gy.data_ptr(), s)
+            out["loss_p"] = loss_p
         self.flat_g.zero_()
         self.engine.backward(self.P, ctx, gy, self.G)
         del ctx
@@ -284,8 +387,15 @@ class Trainer:
         # pdg_loss_reduce writes [flag, nmse / B_global, penalty * div / B_global, total] (one launch for
         # what were torch's sum / scale / add kernels): into the bucket's tail under data parallelism (every
         # rank's shares are already / B_global, so the summed bucket holds the global minibatch's losses)
-        tail = self._bucket[-4:] if self.pg is not None else torch.empty(4, **f32)
-        if fb["B"] > 0:
+        # with physics penalties pdg_loss_reduce_phys writes three more: [.., traction, periodic, mean], each
+        # mu / B_global times its sum, and total includes them
+        tail = self._bucket[-self._tail:] if self.pg is not None else torch.empty(self._tail, **f32)
+        if fb["B"] > 0 and self.physics is not None:
+            ld = fb.get("loss_d")
+            lib.pdg_loss_reduce_phys(fb["B"], fb["loss_g"].data_ptr(), ld.data_ptr() if ld is not None else None,
+                                     fb["loss_p"].data_ptr(), 1.0 / fb["Bn"], self.penalty / fb["Bn"],
+                                     self._phys_scale(fb["Bn"]).data_ptr(), nz.data_ptr(), tail.data_ptr(), s)
+        elif fb["B"] > 0:
             ld = fb.get("loss_d")
             lib.pdg_loss_reduce(fb["B"], fb["loss_g"].data_ptr(), ld.data_ptr() if ld is not None else None,
                                 1.0 / fb["Bn"], self.penalty / fb["Bn"], nz.data_ptr(), tail.data_ptr(), s)
@@ -311,6 +421,8 @@ class Trainer:
         out = {"nmse": vals[0], "total": vals[2], "skipped": skip}      # skipped: valid until the next step
         if self.divergence:
             out["div"] = vals[1]
+        if self.physics is not None:
+            out["traction"], out["periodic"], out["mean"] = vals[3], vals[4], vals[5]
         return out
 
 
