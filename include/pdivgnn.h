@@ -992,6 +992,65 @@ int pdg_loss_reduce_phys(int n_graphs, const float* loss_nmse, const float* loss
                          float scale_nmse, float scale_div, const float* scale_phys, const float* zero_flag,
                          float* out, void* stream);
 
+/* ---------------------------------------------------------------- sampling at arbitrary points */
+/* The operator S that maps a nodal field to its values at query points, and its transpose (pdg_sample.hip).  The
+ * mesh is given as everywhere above: points (n_nodes, dim) fp32 with dim 2 or 3 (x and y are read), faces
+ * (n_faces, nv) int64 with nv 3 or 4 in the face's own vertex order, either orientation.  fp64 arithmetic from the
+ * fp32 inputs, every result rounded to fp32 once; kernel launches only (no host read, no memset node), so every call
+ * can be captured.  Sizes, null pointers (all but the stream) and scratch sizes are refused on the host before any
+ * HIP call; every index read on the device is checked against its array before use.
+ *
+ * pdg_cell_bins.  A uniform gx x gy grid over the mesh's bounding box (bbox: min x, min y, max x, max y, written
+ * here); bin by * gx + bx lists in bin_cells[bin_ptr[bin] .. bin_ptr[bin + 1]) the cells whose own bounding box,
+ * inflated by 8 * 2^-40 of its extents, overlaps the bin (count, exclusive scan, fill; the order inside a bin is
+ * unspecified and nothing depends on it).  bin_ptr: gx gy + 1 ints; bin_cells: `capacity` ints.  info (4 ints):
+ *   0  the total number of entries (saturated at 2^31 - 1),
+ *   1  1 when the total exceeds capacity: no slot at or past capacity was written, bin_cells is incomplete and
+ *      the call is to be repeated with capacity >= info[0],
+ *   2  the number of cells of zero area (det == 0, the det of the mesh fields above): they enter no bin,
+ *   3  the number of cells with a vertex index outside [0, n_nodes): they enter no bin, the index is never used.
+ * scratch holds pdg_cell_bins_scratch_bytes(gx, gy) bytes (< 0 unless gx, gy >= 1 and gx gy + 1024 < 2^31).
+ *
+ * pdg_locate_points.  queries: (n_q, 2) fp32.  With periodic != 0 a query is first wrapped into the box in fp64,
+ * x' = x - floor((x - xmin) / Lx) Lx and the same for y; otherwise a query outside the box is outside.  The
+ * candidates are the cells of the query's bin.  Triangles: barycentric weights, signed sub-area over signed area.
+ * Quads: the closed-form inverse of the bilinear map (the root of the quadratic on which the map's Jacobian has
+ * the sign of the quad's area), weights (1-s)(1-t), s(1-t), st, (1-s)t for (a, b, c, d).  A cell contains the query
+ * iff every weight >= -2^-40; among the containing cells the one whose smallest weight is largest wins, the lowest
+ * cell id among equals.  cell: (n_q) int32, -1 when no cell contains the query (a hole, outside, a NaN query);
+ * weights: (n_q, nv) fp32 with negative weights set to 0, all 0 for -1; *n_outside: the number of -1 (cleared
+ * here).  gx, gy, bin_ptr, bin_cells, capacity, bbox as pdg_cell_bins took and wrote them.
+ *
+ * pdg_sample_field.  out[q, c] = sum_k weights[q, k] field[node_offset + faces[cell[q], k], c], an fp64 sum of
+ * exact products in the order of k; `fill` where cell[q] is -1 (and where an index cannot be used).  field:
+ * (n_rows, n_cols) fp32; node_offset addresses one mesh's rows inside a batched field.
+ *
+ * pdg_sample_csr.  The node-major CSR of S: rowptr (n_nodes + 1) and entries (n_q nv ints, rowptr[n_nodes] of
+ * them used), the entry q nv + k standing for weights[q, k] of a located query whose cell has node n as vertex k;
+ * a row's entries ascend, whatever the atomics' order (the grouping of pdg_graph_plan, rows of any length).
+ * *status: 1 when a cell or a vertex index is out of range (the item is dropped).  scratch holds
+ * pdg_sample_csr_scratch_bytes(n_nodes, n_q, nv) bytes (< 0 for bad sizes).
+ *
+ * pdg_sample_field_bwd.  gfield[n, c] = sum over row n's entries of weights[entry] gout[entry / nv, c], in the
+ * row's order in fp64, rounded once; no atomics, so two calls agree bitwise; a row without entries gets 0.
+ * gout: (n_q, n_cols), gfield: (n_nodes, n_cols). */
+long pdg_cell_bins_scratch_bytes(int gx, int gy);
+int pdg_cell_bins(int n_nodes, const float* points, int dim, int n_faces, int nv, const int64_t* faces, int gx,
+                  int gy, int* bin_ptr, int* bin_cells, long capacity, float* bbox, int* info, void* scratch,
+                  long scratch_bytes, void* stream);
+int pdg_locate_points(int n_nodes, const float* points, int dim, int n_faces, int nv, const int64_t* faces, int gx,
+                      int gy, const int* bin_ptr, const int* bin_cells, long capacity, const float* bbox,
+                      int periodic, long n_q, const float* queries, int* cell, float* weights, int* n_outside,
+                      void* stream);
+int pdg_sample_field(long n_q, int n_faces, int nv, const int64_t* faces, const int* cell, const float* weights,
+                     const float* field, long n_rows, int n_cols, long node_offset, float fill, float* out,
+                     void* stream);
+long pdg_sample_csr_scratch_bytes(int n_nodes, long n_q, int nv);
+int pdg_sample_csr(int n_nodes, int n_faces, int nv, const int64_t* faces, long n_q, const int* cell, int* rowptr,
+                   int* entries, int* status, void* scratch, long scratch_bytes, void* stream);
+int pdg_sample_field_bwd(int n_nodes, long n_q, int nv, const int* rowptr, const int* entries, const float* weights,
+                         const float* gout, int n_cols, float* gfield, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,7 +60,7 @@ def predict_and_save(model: models.EncodeProcessDecode, dataloader: DataLoader, 
 @torch.no_grad()
 def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic: bool = True,
                  divergence: bool = False, enforce_mean: str | None = None, boundary: bool = False,
-                 cells: str = "triangle"):
+                 cells: str = "triangle", *, sample=None):
     """The reference's published workload (``scripts/benchmark_gnn_fem.py:388-415`` then one
     forward) from a bare mesh: ``mesh`` is a legacy-VTK path or a ``(points, faces)`` pair of
     arrays / tensors, ``mean_stress`` the imposed mean field (3 values).  The graph, the node
@@ -79,9 +79,12 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     quad array is refused), ``"quad"`` ((F, 4) faces) or ``"any"`` (decided by the faces' width, which is what a VTK
     file's reader returns): a quad mesh gets the four sides of every quad as edges, its labels, the q1 divergence
     operator, the exact Q1 nodal areas and its boundary vectors from the same device builders
-    (``pdg.devgraph``)."""
+    (``pdg.devgraph``).  ``sample`` (keyword only): query points (Q, 2|3); the returned prediction is also evaluated
+    there (``gnn_local_stress.sampling``: ``PointLocator(points, faces, cells, periodic)``, so with ``periodic`` a
+    point beyond the cell is wrapped into it) and kept as ``data.samples`` (Q, 3), NaN where no cell holds the point,
+    with ``data.sample_plan``; what is returned, and the prediction, are otherwise unchanged."""
     from pdg.devgraph import convert_mesh_to_graph
-    from . import boundary as bd, homogenise, losses, vtk_io
+    from . import boundary as bd, homogenise, losses, sampling, vtk_io
     if enforce_mean is not None:
         homogenise._id(enforce_mean, homogenise.CONVENTIONS, "convention")
     if isinstance(mesh, (str, Path)):
@@ -99,6 +102,10 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     data.local_stress = model.forward(data, scale_output=True, scale_input=True).local_stress
     if enforce_mean is not None:
         data.local_stress = homogenise.enforce_mean(data.local_stress, data, convention=enforce_mean)
+    if sample is not None:
+        xy = torch.as_tensor(sample).to(device=device, dtype=torch.float32)
+        data.sample_plan = sampling.PointLocator(points, faces, cells=cells, periodic=bool(periodic)).locate(xy)
+        data.samples = sampling.sample_field(data.local_stress, data.sample_plan)
     res = bd.boundary_residuals(data.local_stress, data, periodic=bool(periodic)) if boundary else None
     if not divergence:
         return (data, res) if boundary else data

@@ -24,6 +24,12 @@ jump across the periodic connections) are differentiated the same way:
     s = boundary_gradients(model, batch, traction=1.0, periodic=0.0)
     s.value, s.load, s.pos, s.grad_output
 
+The prediction at points that are not nodes (gnn_local_stress.sampling: a virtual strain gauge) takes the samples'
+cotangent to the nodes with S^T first:
+
+    v = sample_gradients(model, batch, plan, grad_samples)
+    v.samples, v.load, v.pos, v.grad_output
+
 The other direction, how the whole field moves when an input moves, is the Jacobian-vector product:
 
     t = input_tangents(model, batch, d_load=...)          # t.local_stress, t.d_local_stress
@@ -253,6 +259,33 @@ def boundary_gradients(model, mesh_graph, traction=1.0, periodic=0.0, scale_outp
         table, _, gy = Bd._grad(Bd._setup(fw.y, mesh_graph, None, None, True), gt, gp)
         g = _vjp_backward(fw, mesh_graph.edge_attr, gy, scale_input)
         return BoundaryGradients(**vars(g), value=value(table), grad_output=gy)
+
+
+@dataclass
+class SampleGradients(InputGradients):
+    """The fields of ``InputGradients`` for the cotangent ``grad_output`` (N, 3) = S^T ``grad_samples``, and
+    ``samples`` (Q, 3), the prediction of the same call at the plan's points (``fill`` where no cell holds one)."""
+    samples: torch.Tensor = None
+    grad_output: torch.Tensor = None
+
+
+def sample_gradients(model, mesh_graph, plan, grad_samples: torch.Tensor, node_offset: int = 0,
+                     fill: float = float("nan"), scale_output: bool = True,
+                     scale_input: bool = True) -> SampleGradients:
+    """The sensitivity of the prediction at arbitrary points (``gnn_local_stress.sampling``: ``plan`` from
+    ``PointLocator.locate``, a virtual strain gauge at every query point) with respect to ``mean_stress``, ``pos``,
+    ``edge_attr`` and each graph's ``load``: ``input_gradients`` with ``grad_output = sample_field_grad(grad_samples,
+    plan)``, the cotangent (Q, 3) on the samples carried to the nodes by S^T, and the samples of the same forward.
+    ``node_offset`` is the first row of the plan's mesh inside a batch (``batch.ptr[g]``).  ``pos`` goes through the
+    node features only: the dependence of the weights on the query and node positions is not chained.  Works with or
+    without ``torch.no_grad()``, never touches a parameter's ``.grad``, raises on CPU tensors."""
+    from . import sampling
+    n = int(mesh_graph.mean_stress.shape[0])
+    with torch.no_grad():
+        gy = sampling.sample_field_grad(grad_samples, plan, n_nodes=n, node_offset=node_offset)
+        g = input_gradients(model, mesh_graph, gy, scale_output, scale_input)
+        samples = sampling.sample_field(g.local_stress, plan, fill, node_offset)
+    return SampleGradients(**vars(g), samples=samples, grad_output=gy)
 
 
 @dataclass

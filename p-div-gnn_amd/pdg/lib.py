@@ -147,6 +147,14 @@ SIGNATURES: dict[str, list] = {
     "pdg_phys_loss_fwd": [I] + [P] * 16,
     "pdg_phys_loss_bwd": [I, P, I] + [P] * 14 + [I, P, P],
     "pdg_loss_reduce_phys": [I, P, P, P, c_float, c_float, P, P, P, P],
+    # sampling at arbitrary points (csrc/pdg_sample.hip)
+    "pdg_cell_bins_scratch_bytes": [I, I],
+    "pdg_cell_bins": [I, P, I, I, I, P, I, I, P, P, ctypes.c_long, P, P, P, ctypes.c_long, P],
+    "pdg_locate_points": [I, P, I, I, I, P, I, I, P, P, ctypes.c_long, P, I, ctypes.c_long, P, P, P, P, P],
+    "pdg_sample_field": [ctypes.c_long, I, I, P, P, P, P, ctypes.c_long, I, ctypes.c_long, c_float, P, P],
+    "pdg_sample_csr_scratch_bytes": [I, ctypes.c_long, I],
+    "pdg_sample_csr": [I, I, I, P, ctypes.c_long, P, P, P, P, P, ctypes.c_long, P],
+    "pdg_sample_field_bwd": [I, ctypes.c_long, I, P, P, P, P, I, P, P],
 }
 # the entry points that return a value, not a status: called as they are (no error check, not counted in
 # lib.calls, not passed to lib.hook)
@@ -155,6 +163,7 @@ _RESTYPES = {"pdg_last_error": ctypes.c_char_p, "pdg_source_hash": ctypes.c_char
              "pdg_mesh_fields_scratch_bytes": ctypes.c_long, "pdg_boundary_vectors_scratch_bytes": ctypes.c_long,
              "pdg_mesh_graph_cells_scratch_bytes": ctypes.c_long, "pdg_mesh_fields_cells_scratch_bytes": ctypes.c_long,
              "pdg_boundary_vectors_cells_scratch_bytes": ctypes.c_long,
+             "pdg_cell_bins_scratch_bytes": ctypes.c_long, "pdg_sample_csr_scratch_bytes": ctypes.c_long,
              "pdg_version": c_int, "pdg_max_blocks": c_int, "pdg_wgrad_slabs_per_cu": c_int, "pdg_pq_layout": c_int}
 
 LN_STAT_BYTES = 40   # sizeof(pdg_ln_stat)
