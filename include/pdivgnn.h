@@ -691,6 +691,47 @@ int pdg_graph_wmean(int n_graphs, const int* ptr, const float* rows, int n_cols,
 int pdg_mean_correct(int n_graphs, const int* ptr, const float* sigma, const double* table, const float* target,
                      const double* denom, float* out, void* stream);
 
+/* ---------------------------------------------------------------- equilibration */
+/* The hard correction for div sigma = 0 (pdg_equil.hip): the field closest to a given one among those whose
+ * divergence vanishes at the interior nodes, and the transpose of that projection.  Per graph of n nodes, with
+ * A = [Dx | Dy] exactly as pdg_div_fwd reads it (a_rowptr / a_col / a_val: CSR over global rows, graph-local
+ * columns, entries with col >= 2 n ignored; at_rowptr / at_row / at_comp / at_val: the same entries by global node,
+ * as pdg_div_plan writes both) and m_v = 1 where node_types[v] == 0, else 0:
+ *   (C s)_x[v] = m_v sum_c (Dx[v,c] sxx[c] + Dy[v,c] sxy[c]),  (C s)_y[v] = m_v sum_c (Dx[v,c] sxy[c] + Dy[v,c] syy[c]).
+ * The metric is |t|^2_W = sum_v w_v (txx^2 + tyy^2 + 2 txy^2), W = diag(w, w, 2 w) on (xx, yy, xy), w = weights
+ * (N, fp32, e.g. the nodal areas of pdg_nodal_areas) or 1 when weights is NULL.  With S = C W^-1 C^T:
+ *   transpose == 0:  S lam = C in,       out = in - W^-1 C^T lam    (P in: C out = 0, |out - in|_W least)
+ *   transpose != 0:  S lam = C W^-1 in,  out = in - C^T lam         (P^T in, the vector-Jacobian product of P)
+ * with (W^-1 C^T lam)_xx[c] = sum_v m_v Dx[v,c] lam_x[v] / w_c, _yy[c] = sum_v m_v Dy[v,c] lam_y[v] / w_c and
+ * _xy[c] = sum_v m_v (Dy[v,c] lam_x[v] + Dx[v,c] lam_y[v]) / (2 w_c).  The system is solved by conjugate gradients
+ * on S from lam = 0: vectors fp32, each row of a product accumulated in fp64 and rounded once, every inner product
+ * an fp64 sum in a fixed order; it stops when the recurrence residual |r|_2 <= rtol |b|_2 (b the right-hand side),
+ * after max_iter iterations, or when p^T S p is not > 0.  in, out: (N, 3) fp32 in xx, yy, xy order, unstandardised;
+ * out is rounded once from fp64.  table: (B, 4) fp64 =
+ *   0  |C in|_2 (transpose: |C W^-1 in|_2), formed in fp64;
+ *   1  the true final residual |C out|_2 (transpose: |C W^-1 out|_2), recomputed in fp64 from the stored fp32 out
+ *      by one more operator application after the loop;
+ *   2  the iterations run;
+ *   3  status bits: 1 the loop ended (max_iter, or p^T S p not > 0) before the recurrence residual fell to
+ *      rtol table[g][0]; 2 the true residual exceeds 2 rtol table[g][0]; 4 a weight of the graph is <= 0 or not
+ *      finite: out is then a bitwise copy of in, columns 0 and 1 are NaN and column 2 is 0.
+ * A graph whose right-hand side is exactly zero (no interior node, no operator entry, in == 0) runs no iteration:
+ * out is a bitwise copy of in and its row is (0, 0, 0, 0).  So is out whenever no iteration ran (max_iter == 0).
+ * A graph without nodes gets NaN in its table row and no field row.  Built like the metrics and homogenisation
+ * kernels: one persistent 1024-thread workgroup per graph, thread t owning rows t, t + 1024, ... in that order,
+ * one kernel launch (no memset or copy node, nothing allocated, no host synchronisation: it can be captured), no
+ * float atomics; a graph gets bitwise the same rows and table row alone and inside any batch, and from call to
+ * call.  scratch holds pdg_equilibrate_scratch_bytes(n_nodes, n_graphs) bytes (11 floats a node; host arithmetic,
+ * < 0 for n_nodes <= 0, n_graphs <= 0 or n_nodes >= 2^29); n_nodes = ptr[n_graphs].  Bad sizes, a NULL pointer
+ * other than weights, rtol not finite and > 0, max_iter < 0, a short scratch and an out that overlaps in are
+ * refused on the host before the launch. */
+long pdg_equilibrate_scratch_bytes(int n_nodes, int n_graphs);
+int pdg_equilibrate(int n_graphs, const int* ptr, int n_nodes, const int* a_rowptr, const int* a_col,
+                    const float* a_val, const int* at_rowptr, const int* at_row, const int* at_comp,
+                    const float* at_val, const int64_t* node_types, const float* weights, const float* in,
+                    int transpose, float rtol, int max_iter, float* out, double* table, void* scratch,
+                    long scratch_bytes, void* stream);
+
 /* ---------------------------------------------------------------- utilities */
 /* out (cols x rows, contiguous) = in^T for a (rows x cols) row-major matrix with row stride ld. */
 int pdg_transpose(int rows, int cols, int ld, const float* in, float* out, void* stream);

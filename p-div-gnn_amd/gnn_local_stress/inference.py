@@ -60,7 +60,8 @@ def predict_and_save(model: models.EncodeProcessDecode, dataloader: DataLoader, 
 @torch.no_grad()
 def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic: bool = True,
                  divergence: bool = False, enforce_mean: str | None = None, boundary: bool = False,
-                 cells: str = "triangle", *, sample=None):
+                 cells: str = "triangle", *, sample=None, equilibrate: bool = False, rtol: float = 1e-5,
+                 max_iter: int = 1000):
     """The reference's published workload (``scripts/benchmark_gnn_fem.py:388-415`` then one
     forward) from a bare mesh: ``mesh`` is a legacy-VTK path or a ``(points, faces)`` pair of
     arrays / tensors, ``mean_stress`` the imposed mean field (3 values).  The graph, the node
@@ -82,9 +83,17 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     (``pdg.devgraph``).  ``sample`` (keyword only): query points (Q, 2|3); the returned prediction is also evaluated
     there (``gnn_local_stress.sampling``: ``PointLocator(points, faces, cells, periodic)``, so with ``periodic`` a
     point beyond the cell is wrapped into it) and kept as ``data.samples`` (Q, 3), NaN where no cell holds the point,
-    with ``data.sample_plan``; what is returned, and the prediction, are otherwise unchanged."""
+    with ``data.sample_plan``; what is returned, and the prediction, are otherwise unchanged.  ``equilibrate``
+    (keyword only): the prediction is projected onto the fields whose divergence vanishes at the interior nodes
+    (``gnn_local_stress.equilibrate.equilibrate`` with the mesh's operator and its nodal areas as weights, both
+    built with the graph, to ``rtol`` in at most ``max_iter`` iterations) before ``enforce_mean`` shifts it:
+    projection, then shift, which with the areas is the closest field that satisfies both.  The solver's (1, 4)
+    fp64 table (``equilibrate.COLUMNS``: defect, true residual, iterations, status bits) is kept as
+    ``data.equilibrate_info`` and returned as one more last value, ``(data, info)`` up to
+    ``(data, div, res, info)``; it stays on the device and is not read here.  Everything after it (``sample``,
+    ``boundary``, ``divergence``) sees the equilibrated field.  False changes nothing."""
     from pdg.devgraph import convert_mesh_to_graph
-    from . import boundary as bd, homogenise, losses, sampling, vtk_io
+    from . import boundary as bd, equilibrate as eq, homogenise, losses, sampling, vtk_io
     if enforce_mean is not None:
         homogenise._id(enforce_mean, homogenise.CONVENTIONS, "convention")
     if isinstance(mesh, (str, Path)):
@@ -97,20 +106,25 @@ def predict_mesh(model: models.EncodeProcessDecode, mesh, mean_stress, periodic:
     if cells == "triangle" and (faces.dim() != 2 or faces.shape[1] != 3):
         raise ValueError(f"predict_mesh takes triangle meshes only (faces of shape (F, 3)) by default, got "
                          f"{tuple(faces.shape)}: pass cells='quad' or cells='any' for a quad mesh")
-    data = convert_mesh_to_graph(points, faces, mean_stress, None, periodic, divergence,
-                                 areas=enforce_mean is not None, boundary=bool(boundary), cells=cells)
+    data = convert_mesh_to_graph(points, faces, mean_stress, None, periodic, bool(divergence or equilibrate),
+                                 areas=enforce_mean is not None or bool(equilibrate), boundary=bool(boundary),
+                                 cells=cells)
     data.local_stress = model.forward(data, scale_output=True, scale_input=True).local_stress
-    if enforce_mean is not None:
+    if equilibrate:
+        data.local_stress, data.equilibrate_info = eq.equilibrate(
+            data.local_stress, data, "area", rtol, max_iter, mean=enforce_mean, return_info=True)
+    elif enforce_mean is not None:
         data.local_stress = homogenise.enforce_mean(data.local_stress, data, convention=enforce_mean)
     if sample is not None:
         xy = torch.as_tensor(sample).to(device=device, dtype=torch.float32)
         data.sample_plan = sampling.PointLocator(points, faces, cells=cells, periodic=bool(periodic)).locate(xy)
         data.samples = sampling.sample_field(data.local_stress, data.sample_plan)
     res = bd.boundary_residuals(data.local_stress, data, periodic=bool(periodic)) if boundary else None
+    tail = (data.equilibrate_info,) if equilibrate else ()
     if not divergence:
-        return (data, res) if boundary else data
+        return (data, res) + tail if boundary else (data,) + tail if tail else data
     div = losses.compute_divergence(data.local_stress, data.op_div_matrix, data.surfaces_nodes_for_div)
-    return (data, div, res) if boundary else (data, div)
+    return ((data, div, res) if boundary else (data, div)) + tail
 
 
 @torch.no_grad()
