@@ -202,6 +202,9 @@ int pdg_decoder_bwd(int n_nodes, const float* gy, const float* a1d, const float*
  * pairs != NULL, pairs[2b..2b+1] = (sum_c g_c row_c, sum_c g_c row_{128+c}) with g = ln_g.  The
  * consumer kernels (pdg_node_bwd, pdg_edge_bwd(_w2), pdg_mlp2_bwd) take these pairs in place of
  * a finalized pdg_ln_bwd and reduce them themselves (S1, S2, c1 = S1/M, c2 = S2/(M std)).
+ * With accumulate == 0 every one of the producer's blocks writes its row and its pair, zeros for a
+ * block without rows, so neither buffer needs a fill and a consumer may reduce all nblocks pairs; with
+ * accumulate != 0 the caller zeroes the accumulator once (the pairs are still written, never added).
  * New in this build: the reference's autograd computes these sums inside the LayerNorm backward
  * (models.py:199,207,265,273). */
 /* Per-channel LayerNorm backward sums over rows: sum gy, sum gy*xhat (xhat from a2 and st);

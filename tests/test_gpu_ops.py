@@ -538,8 +538,8 @@ def test_register_weight_kernels_match_lds_kernels(env, N, res):
     assert lib.pdg_gemm_sum2(N, i0.data_ptr(), i1.data_ptr(), W0T.data_ptr(), W1T.data_ptr(),
                              rr.data_ptr() if res else None, out.data_ptr(), s) == 0
     o.append(out)
-    part = torch.zeros(lib.pdg_max_blocks() * 256, dtype=torch.float64, device="cuda")
-    pairs = torch.zeros(lib.pdg_max_blocks() * 2, dtype=torch.float64, device="cuda")
+    part = torch.full((lib.pdg_max_blocks() * 256,), float("nan"), dtype=torch.float64, device="cuda")
+    pairs = torch.full((lib.pdg_max_blocks() * 2,), float("nan"), dtype=torch.float64, device="cuda")
     npart = ctypes.c_int(0)
     for cols in (False, True):
         out = torch.empty(N, L, device="cuda")
@@ -1003,8 +1003,8 @@ def test_gemm_sum2_coop_vs_fp64(env, N, nb, res):
         ref = ref + rr.double()
     for cols in (False, True):
         out = torch.full((N, L), float("nan"), device="cuda")
-        part = torch.zeros(nb * 256, dtype=torch.float64, device="cuda")
-        pairs = torch.zeros(nb * 2, dtype=torch.float64, device="cuda")
+        part = torch.full((nb * 256,), float("nan"), dtype=torch.float64, device="cuda")
+        pairs = torch.full((nb * 2,), float("nan"), dtype=torch.float64, device="cuda")
         lib.pdg_gemm_sum2_coop(N, i0.data_ptr(), i1.data_ptr(), W0T.data_ptr(), W1T.data_ptr(),
                                rr.data_ptr() if res else None, out.data_ptr(), a2.data_ptr() if cols else None,
                                st.data_ptr() if cols else None, part.data_ptr() if cols else None,
@@ -1130,8 +1130,8 @@ def test_decoder_bwd_coop_vs_decoder_bwd(env, N, nb):
     npart = torch.full((nb * (3 * L + L + 3),), float("nan"), dtype=torch.float64, device="cuda")
     for cols in (False, True):
         z1, x1 = (torch.full((N, L), float("nan"), device="cuda") for _ in range(2))
-        part = torch.zeros(nb * 256, dtype=torch.float64, device="cuda")
-        pairs = torch.zeros(nb * 2, dtype=torch.float64, device="cuda")
+        part = torch.full((nb * 256,), float("nan"), dtype=torch.float64, device="cuda")
+        pairs = torch.full((nb * 2,), float("nan"), dtype=torch.float64, device="cuda")
         assert lib.pdg_decoder_bwd_coop(N, gy.data_ptr(), a1.data_ptr(), Wd2.data_ptr(), W1T.data_ptr(),
                                         z1.data_ptr(), x1.data_ptr(), a2.data_ptr() if cols else None,
                                         st.data_ptr() if cols else None, part.data_ptr() if cols else None,
