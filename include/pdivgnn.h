@@ -1095,6 +1095,67 @@ int pdg_sample_csr(int n_nodes, int n_faces, int nv, const int64_t* faces, long 
 int pdg_sample_field_bwd(int n_nodes, long n_q, int nv, const int* rowptr, const int* entries, const float* weights,
                          const float* gout, int n_cols, float* gfield, void* stream);
 
+/* ---------------------------------------------------------------- FEM targets */
+/* The periodic elastic cell problem on P1 triangles (pdg_fem.hip): plane stress, one isotropic material,
+ * C = E / (1 - nu^2) [[1, nu, 0], [nu, 1, 0], [0, 0, (1 - nu) / 2]] on (xx, yy, xy) with the engineering shear
+ * gamma_xy, u(x) = eps x + ut(x), eps = [[exx, gxy / 2], [gxy / 2, eyy]], ut periodic.  A batch is the concatenation
+ * of its meshes: points (n_nodes, dim) fp32 with dim 2 or 3 (x and y are read), ptr (n_graphs + 1) the node segments,
+ * fptr (n_graphs + 1) the face segments, and, all int32 with batch-wide indices,
+ *   verts (3 n_faces)       the node of every corner, in the face's own vertex order (either orientation),
+ *   rep (n_nodes)           the periodic representative of every node (rep[rep[v]] == rep[v], inside v's graph),
+ *   rverts (3 n_faces)      rep[verts],
+ *   item_rowptr, item       a CSR keyed by representative: row v lists 3 face + corner of every corner that is v or an
+ *                           image of v, ascending; the rows of image nodes are empty.
+ * Every index read on the device is checked against its array before it addresses anything; an item that fails is
+ * skipped.  Sizes, null pointers (all but the stream), the material (young finite and > 0, poisson in (-1, 0.5)) and
+ * the scratch size are refused on the host before any HIP call.
+ *
+ * pdg_fem_elements.  elem (n_faces, 8) fp64 = det, area = |det| / 2, gx[3], gy[3], in fp64 from the fp32
+ * coordinates with the expressions of the P1 divergence operator above, each as written there, contraction off.
+ * *status (cleared here): 1 a face with det == 0 (its gradients are not finite: launch no solve), 2 a vertex outside
+ * [0, n_nodes) (the face's row is NaN).
+ *
+ * pdg_fem_solve.  A = P^T K P, b = -P^T K (eps x) over the representatives, solved by Jacobi-preconditioned
+ * conjugate gradients from x0 = 0; after the preconditioner the mean over the representatives is taken off z, per
+ * component, which keeps the two translations out, and the returned ut has zero mean over the representatives.  One
+ * persistent workgroup of 1024 threads per (graph, load case), grid n_graphs x n_cases: thread t owns the
+ * representatives t, t + 1024, ... of its graph, every product row is gathered by its owner (no scatter), every
+ * inner product is an fp64 block sum folded in a fixed order, no float atomics, nothing allocated, no memset: a graph
+ * gets bitwise the same rows alone and inside any batch, and it can be captured.  strains (n_graphs, n_cases, 3) fp64
+ * = exx, eyy, gxy.  ut (n_cases, n_nodes, 2) fp64: the periodic part at every node (an image holds its
+ * representative's row).  All vectors are fp64 in scratch, pdg_fem_solve_scratch_bytes(n_nodes, n_cases) bytes (x, r,
+ * p, A p, 1 / diag A: 80 bytes per node and case; < 0 unless 0 < n_nodes < 2^29 and 0 < n_cases <= 64).
+ * Termination, all of it decided inside the kernel so that no input makes the workgroup spin:
+ *   noise rule   alongside b the kernel sums b_abs, the same sums with every element term's absolute value; when
+ *                |b|_2 <= 1e-12 |b_abs|_2 the right-hand side is rounding noise (a plate without a hole: the exact
+ *                b is 0): ut = 0, 0 iterations, status TRIVIAL;
+ *   convergence  |r|_2 <= rtol |b|_2 (the recurrence residual; rtol in (0, 1)): status CONVERGED;
+ *   cap          max_iter is clamped to [0, 100000] on the host; reaching it returns the current iterate, MAX_ITER;
+ *   breakdown    p^T A p <= 0 or not finite, or a residual (or b) that is not finite: BREAKDOWN.
+ * table (n_graphs, n_cases, 4) fp64 = iterations, |b|_2, the true final relative residual |b - A x|_2 / |b|_2
+ * recomputed after the loop (0 for TRIVIAL), status (0 CONVERGED, 1 TRIVIAL, 2 MAX_ITER, 3 BREAKDOWN).  An empty
+ * graph (ptr[g + 1] == ptr[g]) gets a NaN table row and nothing else is written for it.
+ *
+ * pdg_fem_stress.  From u = eps x + ut in fp64: the element strains and stresses, and
+ *   stress, strain (n_cases, n_nodes, 3) fp32: the average over the node's own corners (not its images') of the
+ *     incident elements' values, weighted by the element's area (nodal == 0) or unweighted (nodal == 1), the terms
+ *     added in ascending item order and rounded once; 0 for a node of no face;
+ *   sums (n_graphs, n_cases, 8) fp64 = sum area sigma (3), sum area eps (3), the material area, the bounding box's
+ *     area ((xmax - xmin)(ymax - ymin) in fp64 from the fp32 extremes), each a block sum in a fixed order; NaN for an
+ *     empty graph.
+ * Two kernel launches, nothing else: it can be captured. */
+int pdg_fem_elements(int n_nodes, const float* points, int dim, int n_faces, const int* verts, double* elem,
+                     int* status, void* stream);
+long pdg_fem_solve_scratch_bytes(int n_nodes, int n_cases);
+int pdg_fem_solve(int n_graphs, int n_cases, const int* ptr, int n_nodes, const float* points, int dim, int n_faces,
+                  const int* verts, const int* rverts, const int* rep, const int* item_rowptr, const int* item,
+                  const double* elem, const double* strains, double young, double poisson, double rtol, int max_iter,
+                  double* ut, double* table, void* scratch, long scratch_bytes, void* stream);
+int pdg_fem_stress(int n_graphs, int n_cases, const int* ptr, const int* fptr, int n_nodes, const float* points,
+                   int dim, int n_faces, const int* verts, const int* rep, const int* item_rowptr, const int* item,
+                   const double* elem, const double* strains, const double* ut, double young, double poisson,
+                   int nodal, float* stress, float* strain, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
