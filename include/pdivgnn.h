@@ -516,10 +516,11 @@ int pdg_wgrad_slabs_per_cu(void);
 int pdg_wgrad_segments(int nseg, const float* const* g_ptrs, const float* const* x_ptrs, const int* rows,
                        float* slabs, int nslabs, void* stream);
 /* Two weight gradients sharing an operand in one pass over nseg row segments (the shared array is
- * read once): shared_x != 0: slabs0 += A0^T A2, slabs1 += A1^T A2 (bias rows: column sums of A0 /
- * A1); shared_x == 0: slabs0 += A0^T A1, slabs1 += A0^T A2 (bias rows: column sums of A0).  The
- * slabs are written (not accumulated), nslabs each, reduced with pdg_wgrad_reduce.  Pointer and
- * row arrays are HOST arrays of nseg <= PDG_MAX_SEGS entries. */
+ * read once): shared_x != 0: slabs0 = A0^T A2, slabs1 = A1^T A2 (bias rows: column sums of A0 /
+ * A1); shared_x == 0: slabs0 = A0^T A1, slabs1 = A0^T A2 (bias rows: column sums of A0 in both).
+ * Block b writes slab b of both sets with its partial (written, not accumulated; a block without rows
+ * writes zeros), nslabs each, reduced with pdg_wgrad_reduce.  Pointer and row arrays are HOST arrays
+ * of nseg <= PDG_MAX_SEGS entries; a segment of 0 rows may carry NULL pointers. */
 int pdg_wgrad_pairs(int nseg, const float* const* a0_ptrs, const float* const* a1_ptrs, const float* const* a2_ptrs,
                     const int* rows, int shared_x, float* slabs0, float* slabs1, int nslabs, void* stream);
 /* Narrow weight gradient: T[c][i] = sum_k Wide[k][c] Narrow[k][i] (c < 128, i < k_narrow <= 8),

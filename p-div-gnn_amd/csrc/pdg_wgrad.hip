@@ -697,7 +697,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_x6_jobs_kernel2(WgradJobs jobs) 
 
 constexpr size_t WGJ2_SHM = WG_TABLE_FLOATS * 4 + 2 * 2 * WIMG16;
 
-extern "C" int pdg_wgrad_slabs_per_cu(void) { return 3 / 3; }
+extern "C" int pdg_wgrad_slabs_per_cu(void) { return 1; }
 
 extern "C" int pdg_wgrad_segments(int nseg, const float* const* g_ptrs, const float* const* x_ptrs, const int* rows,
                                   float* slabs, int nslabs, void* stream) {

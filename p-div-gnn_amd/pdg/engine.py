@@ -279,7 +279,7 @@ class EPDEngine:
         self._part_narrow_d = torch.empty(self.max_blocks * (L * 3 + L + 3), **f64)
         self._part_narrow_ne = torch.empty(self.max_blocks * (L * 6 + L + 6), **f64)
         self._nparts = ctypes.c_int(0)
-        # one weight-gradient slab per block of pdg_wgrad_segments: three blocks per CU
+        # one weight-gradient slab per block of pdg_wgrad_segments: one 8-wave block per CU
         self._nslabs = lib.pdg_wgrad_slabs_per_cu() * self._cus
         self._nslabs_p = min(var["pair_blocks_per_cu"] * self._cus, self.max_blocks)
         # one 8-wave block per CU: the grid of the cooperative kernels and the slabs of the fused edge backward

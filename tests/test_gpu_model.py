@@ -204,6 +204,77 @@ def test_training_step_matches_oracle_fp32_and_fp64(nmesh, ngraph, steps, diverg
         assert rel(p.grad, g64[name]) <= max(GRAD_TOL, 2 * ref32), (name, rel(p.grad, g64[name]), ref32)
 
 
+@pytest.mark.parametrize("steps,fused,chunked", [(33, True, ("Wa", "Wb", "Wn1a", "Wn1b", "Wn2")),
+                                                  (17, False, ("W2",))])
+def test_more_than_32_segments_match_oracle(steps, fused, chunked):
+    """The engine's chunked deferred weight-gradient path (more than PDG_MAX_SEGS = 32 segments per weight: 32-segment
+    chunks, each reduced at once by pdg_wgrad_reduce before the next chunk overwrites the same slabs) on one 9 x 9
+    hole plate.  steps = 33, fused edge backward: the Wa / Wb and node_net.0 pair passes and node_net.2 have 33
+    segments each (a second chunk of one segment).  steps = 17, fused_edge_wgrad off: edge_net.2 has 17 message + 16
+    edge-update segments.  The segment counts are read from the backward itself and the launches from the library
+    hook, so the test cannot pass without taking the chunked path.  Every gradient against fp64 in the GPU forward's
+    own relu region (a deep network cannot fail on a relu bit), within max(GRAD_TOL, GOLDEN_FACTOR x the fp32
+    oracle's own distance to fp64 in its region): a lost or doubled chunk moves a gradient by percent."""
+    from gnn_local_stress import losses
+    from oracle.epd_oracle import ReluRegion
+    from pdg import meshgen
+    from pdg.lib import lib
+    batch = make_batch([meshgen.hole_plate(9, seed=2)])
+    stats = {k: float(v) for k, v in dataset_stats(batch).items()}
+    model = _model(steps, stats)
+    params = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    eng = model._engine_for(batch.pos.device)
+    eng.fused_edge_wgrad = fused
+    seen, names = {}, []
+    wgrads, epilogue = eng._bwd_wgrads, eng._bwd_epilogue
+
+    def spy_wgrads(b):
+        seen.update({k: len(v) for k, v in b.segs.items()})
+        before, lib.hook = lib.hook, names.append
+        try:
+            return wgrads(b)
+        finally:
+            lib.hook = before
+
+    def spy_epilogue(b):
+        seen["reds"] = len(b.reds)
+        return epilogue(b)
+
+    eng._bwd_wgrads, eng._bwd_epilogue = spy_wgrads, spy_epilogue
+    cap = capture_forward(model)
+    pred = model(batch, scale_output=False).local_stress
+    gt = (batch.local_stress - model.mean_local_stress) / model.std_local_stress
+    total, _, _ = losses.batch_loss(pred, batch, gt, divergence=True, divergence_penalty=10.0)
+    model.zero_grad()
+    total.backward()
+    torch.cuda.synchronize()
+    # the chunked path ran: 33 segments for each weight named, two launches (32 + 1 segments) per pass, every chunk
+    # reduced at once; every other weight in one chunk, its reduction left to the epilogue
+    assert all(seen[k] == 33 for k in chunked), seen
+    assert all(n <= 32 for k, n in seen.items() if k not in chunked and k != "reds"), seen
+    pair_sets = 2 if "Wa" in chunked else 0
+    single = len(chunked) - 2 * pair_sets
+    assert names.count("pdg_wgrad_pairs") == 2 + pair_sets
+    assert names.count("pdg_wgrad_segments") == 2 * single
+    assert names.count("pdg_wgrad_reduce") == 4 * pair_sets + 2 * single
+    a = (params, stats, batch, steps)
+    kw = dict(divergence=True, penalty=10.0)
+    r32 = ReluRegion(keep=True)
+    _, _, g32 = _oracle_grads(*a, torch.float32, region=r32, **kw)
+    _, _, g64_gpu = _oracle_grads(*a, torch.float64, region=ReluRegion(masks=gpu_relu_masks(cap["ctx"])), **kw)
+    _, _, g64_32 = _oracle_grads(*a, torch.float64, region=ReluRegion(masks={k: v > 0 for k, v in r32.keep.items()}),
+                                 **kw)
+    ref32 = {n: rel(g32[n], g64_32[n]) for n in g64_gpu}
+    _log_grads(f"chunked:9x1:s{steps}:fused{int(fused)}", model, g64_gpu, ref32, GOLDEN_FACTOR,
+               extra={"segments": {k: v for k, v in seen.items() if k != "reds"}, "epilogue_reductions": seen["reds"],
+                      "max_fp32_oracle_err": max(ref32.values())})
+    for name, p in model.named_parameters():
+        assert bool(p.grad.isfinite().all()) and bool(g32[name].isfinite().all()), name
+        err = rel(p.grad, g64_gpu[name])
+        print(f"CHUNKED s{steps} fused={int(fused)} {name}: {err:.3e} (fp32 oracle {ref32[name]:.3e})")
+        assert err <= max(GRAD_TOL, GOLDEN_FACTOR * ref32[name]), (name, err, ref32[name])
+
+
 def test_input_gradients_are_refused():
     """Gradients w.r.t. the mesh inputs are not produced by the HIP backward: asking for them
     raises instead of silently returning None."""
