@@ -523,7 +523,7 @@ extern "C" int pdg_node_pq_rw_fin(int n_nodes, const float* a2_prev, const doubl
                                   double count, pdg_ln_stat* st_out, const float* ln_g, const float* ln_b,
                                   const float* x_res, float* x_out, const float* W1, float* P, float* Q,
                                   void* stream) {
-  PDG_CHECK_ARG(partials && st_out && nparts > 0 && nparts < MAX_BLOCKS && count > 0,
+  PDG_CHECK_ARG(partials && st_out && nparts > 0 && nparts <= MAX_BLOCKS && count > 0,
                 "pdg_node_pq_rw_fin: bad statistics arguments");
   return node_pq_rw_launch(n_nodes, a2_prev, nullptr, ln_g, ln_b, x_res, x_out, W1, P, Q, partials, nparts, count,
                            st_out, stream);

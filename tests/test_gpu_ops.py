@@ -1,7 +1,15 @@
-"""Op-level parity of every HIP kernel against a float64 torch restatement of the
-same op (SURVEY §4 tier T1).  Inputs are seeded; sizes include ragged tails
-(rows not a multiple of the 32-row wave tile), zero in-degree nodes and
-repeated indices."""
+"""Op-level parity of the HIP kernels (SURVEY §4 tier T1).  Inputs are seeded; sizes include ragged tails
+(rows not a multiple of the 32-row wave tile), zero in-degree nodes and repeated indices.
+
+Two kinds of test live here.  Against a float64 torch restatement of the same op, stated inline: the tests named
+*_vs_fp64 / *_vs_autograd, test_mlp2_fwd_and_ln_stats, test_encoder_fwd, test_segment_sum_with_layernorm, the
+weight-gradient and loss tests.  Kernel against kernel (bitwise, or to fp32 rounding, with fp64 only as the yardstick
+of which of the two is closer): the tests named *_matches_*, *_equals_* and *_vs_<another kernel>, among them every
+test of the LayerNorm + residual outputs (e_t, x_t, x_S), of pdg_edge_fwd_infer and of the in-kernel statistics;
+they show that two kernels agree, not that either is right.  The reference suites that hold those kernels to fp64
+from their inputs are tests/test_gpu_fwd.py (the per-step forward), tests/test_gpu_edge_bwd.py and
+tests/test_gpu_node_bwd.py (the per-step backward); tests/test_gpu_wgrad.py and tests/test_gpu_loss_ops.py do the
+same for the weight gradients and the kernels that end a step."""
 import ctypes
 
 import pytest
