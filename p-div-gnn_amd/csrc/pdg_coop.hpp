@@ -230,4 +230,160 @@ __device__ __forceinline__ void ln_partial_add(f32x4 a, double& s1, double& s2) 
   s2 += (double)((a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]));
 }
 
+// ---- the per-row code the backward kernels of pdg_ebw.hip, pdg_ingrad.hip and pdg_wgrad.hip share, on the
+// same rule, and the LDS areas their post-loop reductions take (each kernel's layout struct places them).
+
+template <int N>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[N]) {
+#pragma unroll
+  for (int b = 0; b < N; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+}
+
+// d where the relu_mask4 word has its bit set, 0 elsewhere: gz1 = (W^T gz2) [a1 > 0] for 4 features.
+__device__ __forceinline__ f32x4 relu_sel4(unsigned mask_word, const f32x4& d) {
+  f32x4 z;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) z[j] = (mask_word >> (8 * j)) & 1u ? d[j] : 0.f;
+  return z;
+}
+
+// The a1 relu mask of image row r, one word per 4 features (read back per output feature group by gz1_round).
+__device__ __forceinline__ void mask_store4(unsigned char* msk, int r, int cg, const f32x4& a1) {
+  *reinterpret_cast<unsigned*>(msk + r * MSK_STRIDE + 4 * cg) = relu_mask4(a1);
+}
+
+// xhat of 4 features of a LayerNorm input row (ln_relu_bwd4's, pdg_ln_colsum's).
+__device__ __forceinline__ f32x4 xhat4(const f32x4& a2, const LNStat& st) {
+  f32x4 x;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) x[j] = div_den(a2[j] - st.mean, st.den, st.rstd);
+  return x;
+}
+
+constexpr size_t lds_max(size_t a, size_t b) { return a > b ? a : b; }
+constexpr int ROW_GROUPS = EBW_THREADS / 32;                          // threads (rg, cg): 16 rows x 32 column groups
+constexpr size_t SLAB_RED_LDS = ROW_GROUPS * L * sizeof(float);       // slab_accumulate's `red`
+constexpr size_t COLSUMS_LDS = (ROW_GROUPS + 2) * 2 * L * sizeof(double);   // ColSums::emit's red + row + tmp
+
+// The column sums of a LayerNorm backward (sum o, sum o xhat over the block's rows; pdg_ln_colsum's formulas)
+// of thread (rg, cg)'s columns 4cg .. 4cg + 3: fp32 within a 32-row unit, fp64 across units, then the 16 row
+// groups in order through LDS and the block's partial row / pair (lnb_emit).
+struct ColSums {
+  double cs_g[4] = {0, 0, 0, 0}, cs_x[4] = {0, 0, 0, 0};
+  f32x4 sg = f32x4{0.f, 0.f, 0.f, 0.f}, sx = f32x4{0.f, 0.f, 0.f, 0.f};
+  __device__ __forceinline__ void add(const f32x4& o, const f32x4& xhat) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      sg[j] += o[j];
+      sx[j] += o[j] * xhat[j];
+    }
+  }
+  __device__ __forceinline__ void fold() {   // once per 32-row unit
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      cs_g[j] += (double)sg[j];
+      cs_x[j] += (double)sx[j];
+    }
+    sg = sx = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  // `red`: COLSUMS_LDS bytes nobody else reads or writes from the first barrier here on
+  __device__ __forceinline__ void emit(double* red, const float* __restrict__ ln_g, double* __restrict__ part,
+                                       int accumulate, double* __restrict__ pairs) const {
+    const int cg = threadIdx.x & 31, rg = threadIdx.x >> 5;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      red[rg * 2 * L + 4 * cg + j] = cs_g[j];
+      red[rg * 2 * L + L + 4 * cg + j] = cs_x[j];
+    }
+    __syncthreads();
+    double* row = red + ROW_GROUPS * 2 * L;
+    for (int i = threadIdx.x; i < 2 * L; i += EBW_THREADS) {
+      double v = 0;
+      for (int g = 0; g < ROW_GROUPS; ++g) v += red[g * 2 * L + i];
+      row[i] = v;
+    }
+    __syncthreads();
+    lnb_emit(row, ln_g, part, accumulate, pairs, row + 2 * L);
+  }
+};
+
+// A narrow weight gradient T[c][i] = sum_rows wide[c] narrow[i] (c < 128, i < K) in wgrad_narrow_kernel's
+// per-thread form: t = [4 K products | 4 wide sums | K narrow sums] in fp64 for the thread's 4 wide columns;
+// one row's terms, each product rounded to fp32 first.
+template <int K>
+__device__ __forceinline__ void narrow_add(double (&t)[4 * K + 4 + K], const f32x4& wide, const float (&narrow)[K]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) t[c * K + i] += (double)(wide[c] * narrow[i]);
+    t[4 * K + c] += (double)wide[c];
+  }
+#pragma unroll
+  for (int i = 0; i < K; ++i) t[4 * K + 4 + i] += (double)narrow[i];
+}
+
+// LDS of narrow_emit's `red`: 16 row groups x tot doubles
+constexpr size_t narrow_lds(int K) { return (size_t)ROW_GROUPS * (L * K + L + K) * sizeof(double); }
+
+// The block partial of narrow_add's sums in wgrad_narrow_kernel's layout [T (128 K) | wide sums (128) |
+// narrow sums (K)], reduced by pdg_wgrad_narrow_finalize.  Thread (rg, cg) holds columns 4cg .. 4cg + 3 over
+// the rows it visited (the narrow sums counted by the cg = 0 threads only); the 16 row groups are added in
+// order through LDS (`red`: narrow_lds(K) bytes).
+template <int K>
+__device__ __forceinline__ void narrow_emit(const double (&t)[4 * K + 4 + K], double* red, double* __restrict__ out) {
+  constexpr int tot = L * K + L + K;
+  const int cg = threadIdx.x & 31, rg = threadIdx.x >> 5;
+  __syncthreads();   // the caller's LDS is free
+  double* mine = red + rg * tot;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) mine[(4 * cg + c) * K + i] = t[c * K + i];
+    mine[L * K + 4 * cg + c] = t[4 * K + c];
+  }
+  if (cg == 0)
+#pragma unroll
+    for (int i = 0; i < K; ++i) mine[L * K + L + i] = t[4 * K + 4 + i];
+  __syncthreads();
+  for (int e = threadIdx.x; e < tot; e += blockDim.x) {
+    double v = 0;
+    for (int g = 0; g < ROW_GROUPS; ++g) v += red[g * tot + e];
+    out[(size_t)blockIdx.x * tot + e] = v;
+  }
+}
+
+// The stage of the node-type backward kernels for image row r (global row `row`): gz2 = LN_bwd(gy) [a2 > 0],
+// zero past the block's end r1, to its global row (STORE) and the bf16x6 image.
+template <bool STORE>
+__device__ __forceinline__ void gz2_stage4(unsigned char* img2, float* __restrict__ gz2_out, int row, int r1, int r,
+                                           int cg, const f32x4& gy, const f32x4& a2, const LNStat& st,
+                                           const pdg_ln_bwd& lb, const f32x4& g4) {
+  const bool ok = row < r1;
+  const f32x4 z2 = ok ? ln_relu_bwd4(gy, a2, st, lb, g4) : f32x4{0.f, 0.f, 0.f, 0.f};
+  if (STORE && ok) stnt4(gz2_out + (size_t)row * L + 4 * cg, z2);
+  img_store4(img2, r, cg, z2);
+}
+
+// gz1 = (W2^T gz2) [a1 > 0] of a 32-row round from the gz2 image and the mask_store4 words, into the fp32 row
+// tile t_z (and, IMG, the next product's image).
+template <bool IMG>
+__device__ __forceinline__ void gz1_round(const WSlice& w2, const unsigned char* img2, const unsigned char* msk,
+                                          float* t_z, unsigned char* img1) {
+  const int l = lane_id(), w = wave_id();
+  const int oc = 16 * w + 4 * (l >> 4);
+  f32x4 d[1][2];
+  const unsigned char* imgs[1] = {img2};
+  gemm_round<1>(d, w2, imgs);
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb) {
+    const int r = 16 * nb + (l & 15);
+    const f32x4 z1 = relu_sel4(*reinterpret_cast<const unsigned*>(msk + r * MSK_STRIDE + oc), d[0][nb]);
+    if (IMG) img_store4(img1, r, 4 * w + (l >> 4), z1);
+    *reinterpret_cast<f32x4*>(t_z + r * OT_STRIDE + oc) = z1;
+  }
+}
+
 }  // namespace

@@ -42,6 +42,15 @@ using namespace pdg;
 // order (message and edge-update rows of a round interleave per 16 rows instead of per 32).
 // (A form recomputing a1m / a1e from the forward's C = Wc e + b1 and the step's gathered P / Q rows,
 // one E-row array read and written fewer, measured slower and was removed: DESIGN §4 round 3.)
+// LDS: two rounds' buffers of images (gz2m, a1m; EU: gz2e, a1e) and relu masks; afterwards slab_accumulate's red.
+template <bool EU>
+struct W2Lds {
+  static constexpr int NIMG = EU ? 4 : 2, NMSK = EU ? 2 : 1;
+  static constexpr int BUF = NIMG * IMG16 + NMSK * MSK16;   // one round's images + masks
+  static constexpr size_t total = 2 * BUF;
+  static_assert(SLAB_RED_LDS <= total, "slab_accumulate's red inside the (dead) buffers");
+};
+
 template <bool EU>
 __global__ __launch_bounds__(EBW_THREADS, 1) void edge_bwd_w2_kernel(
     const int* __restrict__ dst, const float* __restrict__ gaggr, const float* __restrict__ ge_next,
@@ -52,8 +61,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_bwd_w2_kernel(
     float* __restrict__ slabs, int E, const double* __restrict__ pm, int npm, const double* __restrict__ pe,
     int npe, int slab_init) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
-  constexpr int NIMG = EU ? 4 : 2, NMSK = EU ? 2 : 1;
-  constexpr int BUF = NIMG * IMG16 + NMSK * MSK16;           // one round's images + masks
+  constexpr int NIMG = W2Lds<EU>::NIMG, BUF = W2Lds<EU>::BUF;
   const int l = lane_id(), w = wave_id();
   const int cg = threadIdx.x & 31, rg = threadIdx.x >> 5;    // the thread's staged row: rg (0..15)
   const int oc = 16 * w + 4 * (l >> 4);
@@ -126,14 +134,14 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_bwd_w2_kernel(
       bsum += zm;
       img_store4<T16>(img_gm, rg, cg, zm);
       img_store4<T16>(img_am, rg, cg, am);
-      *reinterpret_cast<unsigned*>(msk_m + rg * MSK_STRIDE + 4 * cg) = relu_mask4(am);
+      mask_store4(msk_m, rg, cg, am);
       if (EU) {
         const f32x4 ze = ok ? ln_relu_bwd4(pge[s], pa2e[s], ste, lbe, g4) : zero;
         const f32x4 ae = a1ev;
         bsum += ze;
         img_store4<T16>(img_ge, rg, cg, ze);
         img_store4<T16>(img_ae, rg, cg, ae);
-        *reinterpret_cast<unsigned*>(msk_e + rg * MSK_STRIDE + 4 * cg) = relu_mask4(ae);
+        mask_store4(msk_e, rg, cg, ae);
       }
     }
     // ---- the set is free: its rows of the round after next (the same half of the next unit), then
@@ -161,7 +169,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_bwd_w2_kernel(
     const int r = l & 15;
     const int row = base + r;
     const unsigned mm = *reinterpret_cast<const unsigned*>(msk_m + r * MSK_STRIDE + oc);
-    f32x4 zm;
+    f32x4 zm;   // relu_sel4, written out here and below (this kernel's ISA is pinned: EXPERIMENTS §10)
 #pragma unroll
     for (int j = 0; j < 4; ++j) zm[j] = (mm >> (8 * j)) & 1u ? d[0][0][j] : 0.f;
     f32x4 c = zm;
@@ -206,6 +214,16 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_bwd_w2_kernel(
 // epilogues add into one fp32 sum before it is folded into the fp64 one); 125.7 -> 122.0 us per config-2
 // call (same box, EXPERIMENTS §5).
 constexpr int GO_TILE = R16 * OT_STRIDE;   // floats per 16-row output tile
+// LDS of the two-parity pipeline (edge_gout_wc_kernel, gemm_sum2_coop_kernel): two rounds' images of the two
+// operands, two output tiles.  After the loop, with images and tiles dead: slab_accumulate's red (edge_gout_wc)
+// and ColSums::emit's area (at 16 KB behind the red in edge_gout_wc, at 0 in gemm_sum2_coop).
+struct PipeLds {
+  static constexpr size_t tile = 4 * IMG16;
+  static constexpr size_t total = tile + 2 * GO_TILE * sizeof(float);
+  static constexpr size_t gout_cols = 2 * SLAB_RED_LDS;
+  static_assert(SLAB_RED_LDS <= gout_cols && gout_cols + COLSUMS_LDS <= total, "edge_gout_wc's reductions");
+  static_assert(COLSUMS_LDS <= total, "gemm_sum2_coop's reduction");
+};
 template <bool RES, bool LN>
 __global__ __launch_bounds__(EBW_THREADS, 1) void edge_gout_wc_kernel(
     const float* __restrict__ gC, const float* __restrict__ e, const float* __restrict__ ge_next,
@@ -214,7 +232,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_gout_wc_kernel(
     const float* __restrict__ ln_g, double* __restrict__ pairs, int accumulate, int slab_init) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   unsigned char* img = sm;                                           // [parity][gC, e] 16-row images
-  float* tile = reinterpret_cast<float*>(sm + 4 * IMG16);            // [parity] Wc^T gC rows
+  float* tile = reinterpret_cast<float*>(sm + PipeLds::tile);        // [parity] Wc^T gC rows
   LNStat stln;
   if (LN) stln = *reinterpret_cast<const LNStat*>(stln_p);
   const int l = lane_id(), w = wave_id();
@@ -230,8 +248,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_gout_wc_kernel(
     for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
   f32x4 bsum = f32x4{0.f, 0.f, 0.f, 0.f};
   const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-  double cs_g[4] = {0, 0, 0, 0}, cs_x[4] = {0, 0, 0, 0};
-  f32x4 sg = zero, sx = zero;   // the current 32-row unit's column sums (fp32, as edge_gout_wc_kernel's)
+  ColSums cs;
   const __amdgpu_buffer_rsrc_t rs_out = rows_rsrc(ge_out, r0, r1);
   f32x4 pc[2], pe[2], pres[2], pa2[2];   // rows in flight, by round parity
   f32x4 hres[2], hx[2];                  // a staged round's residual and xhat, held to its epilogue
@@ -249,10 +266,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_gout_wc_kernel(
     img_store4<T16>(img + (2 * s) * IMG16, rg, cg, c);
     img_store4<T16>(img + (2 * s + 1) * IMG16, rg, cg, ok ? pe[s] : zero);
     hres[s] = RES ? pres[s] : zero;
-    if (LN) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) hx[s][j] = div_den(pa2[s][j] - stln.mean, stln.den, stln.rstd);
-    }
+    if (LN) hx[s] = xhat4(pa2[s], stln);
     issue(s, base + stride);
   };
   auto compute = [&](const int s) {
@@ -267,24 +281,10 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_gout_wc_kernel(
     const f32x4 dv = *reinterpret_cast<const f32x4*>(tile + s * GO_TILE + rg * OT_STRIDE + 4 * cg);
     const f32x4 go = RES ? hres[s] + dv : dv;
     rows_store4(rs_out, row - r0, 4 * cg, go);   // rows outside [r0, r1) dropped by the range
-    if (LN && row >= r0 && row < r1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sg[j] += go[j];
-        sx[j] += go[j] * hx[s][j];
-      }
-    }
+    if (LN && row >= r0 && row < r1) cs.add(go, hx[s]);
   };
   auto fold = [&]() {   // a unit's two epilogues done
-    if (LN) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        cs_g[j] += (double)sg[j];
-        cs_x[j] += (double)sx[j];
-      }
-      sg = zero;
-      sx = zero;
-    }
+    if (LN) cs.fold();
   };
   // each set's loads strictly before the next set's, in the loop's re-issue order
   issue(0, first);
@@ -311,19 +311,19 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_gout_wc_kernel(
   __syncthreads();   // the last tile reads precede the LDS reuse below
   slab_accumulate(slabs + (size_t)blockIdx.x * WSLAB, acc, bsum, reinterpret_cast<float*>(sm), slab_init);
   if (LN) {
-    // block partial = the 16 row groups' column sums, reduced in order through LDS (after slab_accumulate's 8 KB)
-    double* red = reinterpret_cast<double*>(sm + 16384);
+    // ColSums::emit, written out: called here it costs this kernel 2 VGPRs (EXPERIMENTS §10)
+    double* red = reinterpret_cast<double*>(sm + PipeLds::gout_cols);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      red[rg * 2 * L + 4 * cg + j] = cs_g[j];
-      red[rg * 2 * L + L + 4 * cg + j] = cs_x[j];
+      red[rg * 2 * L + 4 * cg + j] = cs.cs_g[j];
+      red[rg * 2 * L + L + 4 * cg + j] = cs.cs_x[j];
     }
     __syncthreads();
-    double* row = red + EBW_THREADS / 32 * 2 * L;
+    double* row = red + ROW_GROUPS * 2 * L;
     for (int i = threadIdx.x; i < 2 * L; i += blockDim.x) {
       double v = 0;
-      for (int g = 0; g < EBW_THREADS / 32; ++g) v += red[g * 2 * L + i];
+      for (int g = 0; g < ROW_GROUPS; ++g) v += red[g * 2 * L + i];
       row[i] = v;
     }
     __syncthreads();
@@ -410,8 +410,8 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void gemm_sum2_coop_kernel(
     const float* __restrict__ ln_g, double* __restrict__ pairs, int accumulate) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   unsigned char* img = sm;                                        // [parity][in0, in1] 16-row images
-  float* tile = reinterpret_cast<float*>(sm + 4 * IMG16);         // [parity] output rows
-  constexpr int TL = R16 * OT_STRIDE;
+  float* tile = reinterpret_cast<float*>(sm + PipeLds::tile);     // [parity] output rows
+  constexpr int TL = GO_TILE;
   LNStat stln;
   if (COLS) stln = *reinterpret_cast<const LNStat*>(ln_st);
   const int l = lane_id(), w = wave_id();
@@ -421,8 +421,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void gemm_sum2_coop_kernel(
   block_rows(N, r0, r1);
   WSlice ws0, ws1;
   const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-  double cs_g[4] = {0, 0, 0, 0}, cs_x[4] = {0, 0, 0, 0};
-  f32x4 sg = zero, sx = zero;
+  ColSums cs;
   const __amdgpu_buffer_rsrc_t rs_out = rows_rsrc(out, r0, r1);
   f32x4 p0[2], p1[2], pres[2], pa2[2], hres[2], hx[2];
   auto issue = [&](int s, int base) {
@@ -437,10 +436,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void gemm_sum2_coop_kernel(
     img_store4<T16>(img + (2 * s) * IMG16, rg, cg, ok ? p0[s] : zero);
     img_store4<T16>(img + (2 * s + 1) * IMG16, rg, cg, ok ? p1[s] : zero);
     hres[s] = RES ? pres[s] : zero;
-    if (COLS) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) hx[s][j] = div_den(pa2[s][j] - stln.mean, stln.den, stln.rstd);
-    }
+    if (COLS) hx[s] = xhat4(pa2[s], stln);
     issue(s, base + X6_ROWS);
   };
   auto compute = [&](const int s) {
@@ -452,24 +448,10 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void gemm_sum2_coop_kernel(
     const int row = base + rg;
     const f32x4 o = *reinterpret_cast<const f32x4*>(tile + s * TL + rg * OT_STRIDE + 4 * cg) + hres[s];
     rows_store4(rs_out, row - r0, 4 * cg, o);
-    if (COLS && row >= r0 && row < r1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sg[j] += o[j];
-        sx[j] += o[j] * hx[s][j];
-      }
-    }
+    if (COLS && row >= r0 && row < r1) cs.add(o, hx[s]);
   };
   auto fold = [&]() {
-    if (COLS) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        cs_g[j] += (double)sg[j];
-        cs_x[j] += (double)sx[j];
-      }
-      sg = zero;
-      sx = zero;
-    }
+    if (COLS) cs.fold();
   };
   issue(0, r0);   // N > 0: an empty block (r0 = r1 = N) reads row N - 1
   __builtin_amdgcn_sched_barrier(0);
@@ -493,24 +475,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void gemm_sum2_coop_kernel(
   __syncthreads();
   epilogue(1, last + R16);
   fold();
-  if (COLS) {
-    double* red = reinterpret_cast<double*>(sm);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      red[rg * 2 * L + 4 * cg + j] = cs_g[j];
-      red[rg * 2 * L + L + 4 * cg + j] = cs_x[j];
-    }
-    __syncthreads();
-    double* row = red + EBW_THREADS / 32 * 2 * L;
-    for (int i = threadIdx.x; i < 2 * L; i += blockDim.x) {
-      double v = 0;
-      for (int g = 0; g < EBW_THREADS / 32; ++g) v += red[g * 2 * L + i];
-      row[i] = v;
-    }
-    __syncthreads();
-    lnb_emit(row, ln_g, part, accumulate, pairs, row + 2 * L);
-  }
+  if (COLS) cs.emit(reinterpret_cast<double*>(sm), ln_g, part, accumulate, pairs);
 }
 
 // ============================================================================ node_net backward
@@ -549,6 +514,11 @@ __device__ __forceinline__ void gemm_round_2w(f32x4 (&da)[2], f32x4 (&db)[2], co
     }
 }
 
+struct NodeBwdLds {   // images of gz2 and gz1, the a1 mask, four fp32 row tiles; no post-loop area
+  static constexpr size_t img1 = EBW_IMG, msk = 2 * EBW_IMG, tiles = msk + EBW_MASK;
+  static constexpr size_t total = tiles + 4 * EFC_TILE * sizeof(float);
+};
+
 __global__ __launch_bounds__(EBW_THREADS, 1) void node_bwd_coop_kernel(
     int N, const float* __restrict__ gy, const float* __restrict__ a2, const float* __restrict__ a1,
     const pdg_ln_stat* __restrict__ stp, const pdg_ln_bwd* __restrict__ lbp, const double* __restrict__ lb_pairs,
@@ -557,9 +527,9 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void node_bwd_coop_kernel(
     float* __restrict__ gaggr, float* __restrict__ gx_part) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   unsigned char* img2 = sm;                                    // gz2
-  unsigned char* img1 = sm + EBW_IMG;                          // gz1
-  unsigned char* msk = sm + 2 * EBW_IMG;                       // [a1 > 0]
-  float* t_z = reinterpret_cast<float*>(msk + EBW_MASK);       // gz1 rows
+  unsigned char* img1 = sm + NodeBwdLds::img1;                 // gz1
+  unsigned char* msk = sm + NodeBwdLds::msk;                   // [a1 > 0]
+  float* t_z = reinterpret_cast<float*>(sm + NodeBwdLds::tiles);   // gz1 rows
   float* t_a = t_z + EFC_TILE;                                 // W1a^T gz1
   float* t_b = t_a + EFC_TILE;                                 // W1b^T gz1
   float* t_g = t_b + EFC_TILE;                                 // gy rows (the residual; no registers)
@@ -587,34 +557,16 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void node_bwd_coop_kernel(
   };
   if (r0 < r1) issue(r0);
   for (int base = r0; base < r1; base += X6_ROWS) {
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = rg + 16 * u;
-      const bool ok = base + r < r1;
-      const f32x4 z2 = ok ? ln_relu_bwd4(pg[u], pa2[u], st, lb, g4) : zero;
-      if (ok) stnt4(gz2_out + (size_t)(base + r) * L + 4 * cg, z2);
-      img_store4(img2, r, cg, z2);
-      *reinterpret_cast<unsigned*>(msk + r * MSK_STRIDE + 4 * cg) = relu_mask4(pa1[u]);
+      gz2_stage4<true>(img2, gz2_out, base + r, r1, r, cg, pg[u], pa2[u], st, lb, g4);
+      mask_store4(msk, r, cg, pa1[u]);
       *reinterpret_cast<f32x4*>(t_g + r * OT_STRIDE + 4 * cg) = pg[u];
     }
     __syncthreads();   // gz2 image and the a1 mask complete
     if (base + X6_ROWS < r1) issue(base + X6_ROWS);
-    {
-      f32x4 d[1][2];
-      const unsigned char* imgs[1] = {img2};
-      gemm_round<1>(d, w2, imgs);
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        const int r = 16 * nb + (l & 15);
-        const unsigned mm = *reinterpret_cast<const unsigned*>(msk + r * MSK_STRIDE + oc);
-        f32x4 z1;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) z1[j] = (mm >> (8 * j)) & 1u ? d[0][nb][j] : 0.f;   // relu_mask_acc
-        img_store4(img1, r, 4 * w + (l >> 4), z1);
-        *reinterpret_cast<f32x4*>(t_z + r * OT_STRIDE + oc) = z1;
-      }
-    }
+    gz1_round<true>(w2, img2, msk, t_z, img1);
     __syncthreads();   // gz1 image complete
     {
       f32x4 da[2], db[2];
@@ -642,40 +594,18 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void node_bwd_coop_kernel(
   }
 }
 
-// ============================================================================ narrow weight gradients
-// The block partial of a narrow weight gradient T[c][i] = sum_rows wide[c] narrow[i] (c < 128, i < K) in
-// wgrad_narrow_kernel's layout [T (128 K) | wide sums (128) | narrow sums (K)], reduced by
-// pdg_wgrad_narrow_finalize.  Thread (rg, cg) holds the fp64 sums of columns 4cg .. 4cg + 3 over the rows
-// it visited (t[4 K + 4 + K]: products, wide sums, narrow sums — the narrow sums counted by the cg = 0
-// threads only); the 16 row groups are added in order through LDS (`red`: 16 x tot doubles).
-template <int K>
-__device__ __forceinline__ void narrow_emit(const double (&t)[4 * K + 4 + K], double* red, double* __restrict__ out) {
-  constexpr int tot = L * K + L + K;
-  const int cg = threadIdx.x & 31, rg = threadIdx.x >> 5;
-  __syncthreads();   // the caller's LDS is free
-  double* mine = red + rg * tot;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-#pragma unroll
-    for (int i = 0; i < K; ++i) mine[(4 * cg + c) * K + i] = t[c * K + i];
-    mine[L * K + 4 * cg + c] = t[4 * K + c];
-  }
-  if (cg == 0)
-#pragma unroll
-    for (int i = 0; i < K; ++i) mine[L * K + L + i] = t[4 * K + 4 + i];
-  __syncthreads();
-  for (int e = threadIdx.x; e < tot; e += blockDim.x) {
-    double v = 0;
-    for (int g = 0; g < EBW_THREADS / 32; ++g) v += red[g * tot + e];
-    out[(size_t)blockIdx.x * tot + e] = v;
-  }
-}
-
 // ============================================================================ encoder backward
 // pdg_mlp2_bwd in the cooperative layout (the node encoder's backward, models.py:264-275 for the
 // 6-input encoder): gz2 = LN_bwd(gy) [a2 > 0] (whole rows -> HBM and a bf16x6 image),
 // gz1 = (W2^T gz2) [a1 > 0] (the product in bf16x6 with W2^T in registers) -> row tile -> HBM.
 // node_bwd_coop_kernel's first half.
+struct Mlp2BwdLds {   // the gz2 image, the a1 mask, the gz1 row tile; afterwards (narrow) narrow_emit<6>'s red
+  static constexpr size_t msk = EBW_IMG, tile = msk + EBW_MASK;
+  static constexpr size_t total(bool narrow) {
+    return lds_max(tile + EFC_TILE * sizeof(float), narrow ? narrow_lds(6) : 0);
+  }
+};
+
 __global__ __launch_bounds__(EBW_THREADS, 1) void mlp2_bwd_coop_kernel(
     int N, const float* __restrict__ gy, const float* __restrict__ a2, const float* __restrict__ a1,
     const pdg_ln_stat* __restrict__ stp, const pdg_ln_bwd* __restrict__ lbp, const double* __restrict__ lb_pairs,
@@ -683,24 +613,22 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void mlp2_bwd_coop_kernel(
     float* __restrict__ gz1_out, const float* __restrict__ xn, double* __restrict__ npart) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   unsigned char* img2 = sm;                                    // gz2
-  unsigned char* msk = sm + EBW_IMG;                           // [a1 > 0]
-  float* t_z = reinterpret_cast<float*>(msk + EBW_MASK);       // gz1 rows
-  const int l = lane_id(), w = wave_id();
+  unsigned char* msk = sm + Mlp2BwdLds::msk;                   // [a1 > 0]
+  float* t_z = reinterpret_cast<float*>(sm + Mlp2BwdLds::tile);   // gz1 rows
   const int cg = threadIdx.x & 31, rg = threadIdx.x >> 5;
-  const int oc = 16 * w + 4 * (l >> 4);
   int r0, r1;
   block_rows(N, r0, r1);
   WSlice w2;
-  load_wslice(w2, W2T, w);
+  load_wslice(w2, W2T, wave_id());
   const LNStat st = *reinterpret_cast<const LNStat*>(stp);
   const pdg_ln_bwd lb = lnb_resolve(lbp, lb_pairs, lb_npairs, stp);
   const f32x4 g4 = *reinterpret_cast<const f32x4*>(lg + 4 * cg);
-  // xn != NULL: the first layer's weight gradient from the gz1 rows of the epilogue (wgrad_narrow_kernel<6>'s
-  // products and order per row, wide = gz1, narrow = xn = the encoder input), gz1 itself not needed
-  constexpr int NK = 6, NT = 4 * NK + 4 + NK;
-  double nt[NT];
+  // xn != NULL: the first layer's weight gradient from the gz1 rows of the epilogue (narrow_add, wide = gz1,
+  // narrow = xn = the encoder input), gz1 itself not needed
+  constexpr int NK = 6;
+  double nt[4 * NK + 4 + NK];
 #pragma unroll
-  for (int p = 0; p < NT; ++p) nt[p] = 0;
+  for (int p = 0; p < 4 * NK + 4 + NK; ++p) nt[p] = 0;
   f32x4 pg[2], pa2[2], pa1[2];
   float px[2][NK], xv[2][NK];
   auto issue = [&](int base) {
@@ -718,32 +646,17 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void mlp2_bwd_coop_kernel(
   };
   if (r0 < r1) issue(r0);
   for (int base = r0; base < r1; base += X6_ROWS) {
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = rg + 16 * u;
-      const bool ok = base + r < r1;
-      const f32x4 z2 = ok ? ln_relu_bwd4(pg[u], pa2[u], st, lb, g4) : zero;
-      if (ok) stnt4(gz2_out + (size_t)(base + r) * L + 4 * cg, z2);
-      img_store4(img2, r, cg, z2);
-      *reinterpret_cast<unsigned*>(msk + r * MSK_STRIDE + 4 * cg) = relu_mask4(pa1[u]);
+      gz2_stage4<true>(img2, gz2_out, base + r, r1, r, cg, pg[u], pa2[u], st, lb, g4);
+      mask_store4(msk, r, cg, pa1[u]);
 #pragma unroll
       for (int i = 0; i < NK; ++i) xv[u][i] = px[u][i];
     }
     __syncthreads();   // gz2 image and the a1 mask complete
     if (base + X6_ROWS < r1) issue(base + X6_ROWS);
-    f32x4 d[1][2];
-    const unsigned char* imgs[1] = {img2};
-    gemm_round<1>(d, w2, imgs);
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-      const int r = 16 * nb + (l & 15);
-      const unsigned mm = *reinterpret_cast<const unsigned*>(msk + r * MSK_STRIDE + oc);
-      f32x4 z1;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) z1[j] = (mm >> (8 * j)) & 1u ? d[0][nb][j] : 0.f;   // relu_mask_acc
-      *reinterpret_cast<f32x4*>(t_z + r * OT_STRIDE + oc) = z1;
-    }
+    gz1_round<false>(w2, img2, msk, t_z, nullptr);
     __syncthreads();   // the gz1 tile is complete; image and mask free for the next round
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -751,16 +664,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void mlp2_bwd_coop_kernel(
       if (base + r < r1) {
         const f32x4 z1 = *reinterpret_cast<const f32x4*>(t_z + r * OT_STRIDE + 4 * cg);
         if (gz1_out) stnt4(gz1_out + (size_t)(base + r) * L + 4 * cg, z1);
-        if (xn) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-#pragma unroll
-            for (int i = 0; i < NK; ++i) nt[c * NK + i] += (double)(z1[c] * xv[u][i]);
-            nt[4 * NK + c] += (double)z1[c];
-          }
-#pragma unroll
-          for (int i = 0; i < NK; ++i) nt[4 * NK + 4 + i] += (double)xv[u][i];
-        }
+        if (xn) narrow_add<NK>(nt, z1, xv[u]);
       }
     }
   }
@@ -773,6 +677,13 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void mlp2_bwd_coop_kernel(
 //   gx   = Wd1^T gz1d           (bf16x6, Wd1^T stationary in registers)
 // COLS: gx is the upstream gradient of the last node LayerNorm; its pdg_ln_colsum column sums /
 // (S1, S2) pairs are formed from the row tile (gemm_sum2_coop_kernel's reduction).
+struct DecBwdLds {   // the gz1d image and the gx row tile; afterwards ColSums::emit's area, then narrow_emit<3>'s red
+  static constexpr size_t tile = EBW_IMG;
+  static constexpr size_t total(bool cols, bool narrow) {
+    return lds_max(tile + EFC_TILE * sizeof(float), lds_max(cols ? COLSUMS_LDS : 0, narrow ? narrow_lds(3) : 0));
+  }
+};
+
 template <bool COLS>
 __global__ __launch_bounds__(EBW_THREADS, 1) void decoder_bwd_coop_kernel(
     int N, const float* __restrict__ gy, const float* __restrict__ a1d, const float* __restrict__ Wd2,
@@ -781,13 +692,12 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void decoder_bwd_coop_kernel(
     const float* __restrict__ ln_g, double* __restrict__ pairs, int accumulate, double* __restrict__ npart) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   unsigned char* img = sm;
-  float* t_o = reinterpret_cast<float*>(sm + EBW_IMG);
-  // npart != NULL: node_decoder.2's weight gradient from the staged rows (wgrad_narrow_kernel<3>'s products
-  // per row, wide = a1d, narrow = gy)
-  constexpr int NK = 3, NT = 4 * NK + 4 + NK;
-  double nt[NT];
+  float* t_o = reinterpret_cast<float*>(sm + DecBwdLds::tile);
+  // npart != NULL: node_decoder.2's weight gradient from the staged rows (narrow_add, wide = a1d, narrow = gy)
+  constexpr int NK = 3;
+  double nt[4 * NK + 4 + NK];
 #pragma unroll
-  for (int p = 0; p < NT; ++p) nt[p] = 0;
+  for (int p = 0; p < 4 * NK + 4 + NK; ++p) nt[p] = 0;
   LNStat stln;
   if (COLS) stln = *reinterpret_cast<const LNStat*>(ln_st);
   const int l = lane_id(), w = wave_id();
@@ -800,7 +710,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void decoder_bwd_coop_kernel(
   f32x4 wd[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) wd[k] = *reinterpret_cast<const f32x4*>(Wd2 + k * L + 4 * cg);
-  double cs_g[4] = {0, 0, 0, 0}, cs_x[4] = {0, 0, 0, 0};
+  ColSums cs;
   f32x4 pa1[2], pa2[2];
   float pg[2][3];
   auto issue = [&](int base) {
@@ -830,16 +740,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void decoder_bwd_coop_kernel(
       if (ok) stnt4(gz1d + (size_t)(base + r) * L + 4 * cg, z);
       img_store4(img, r, cg, z);
       av[u] = COLS ? pa2[u] : zero;
-      if (npart && ok) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-          for (int i = 0; i < NK; ++i) nt[c * NK + i] += (double)(pa1[u][c] * pg[u][i]);
-          nt[4 * NK + c] += (double)pa1[u][c];
-        }
-#pragma unroll
-        for (int i = 0; i < NK; ++i) nt[4 * NK + 4 + i] += (double)pg[u][i];
-      }
+      if (npart && ok) narrow_add<NK>(nt, pa1[u], pg[u]);
     }
     __syncthreads();   // image complete
     if (base + X6_ROWS < r1) issue(base + X6_ROWS);
@@ -849,7 +750,6 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void decoder_bwd_coop_kernel(
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) *reinterpret_cast<f32x4*>(t_o + (16 * nb + (l & 15)) * OT_STRIDE + oc) = d[0][nb];
     __syncthreads();   // tile complete; the image is free for the next round
-    f32x4 sg = zero, sx = zero;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = rg + 16 * u;
@@ -857,41 +757,12 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void decoder_bwd_coop_kernel(
       if (row < r1) {
         const f32x4 o = *reinterpret_cast<const f32x4*>(t_o + r * OT_STRIDE + 4 * cg);
         stg4(gx + (size_t)row * L + 4 * cg, o);
-        if (COLS) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {   // the pdg_ln_colsum formulas
-            sg[j] += o[j];
-            sx[j] += o[j] * div_den(av[u][j] - stln.mean, stln.den, stln.rstd);
-          }
-        }
+        if (COLS) cs.add(o, xhat4(av[u], stln));
       }
     }
-    if (COLS) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        cs_g[j] += (double)sg[j];
-        cs_x[j] += (double)sx[j];
-      }
-    }
+    if (COLS) cs.fold();
   }
-  if (COLS) {
-    double* red = reinterpret_cast<double*>(sm);
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      red[rg * 2 * L + 4 * cg + j] = cs_g[j];
-      red[rg * 2 * L + L + 4 * cg + j] = cs_x[j];
-    }
-    __syncthreads();
-    double* row = red + EBW_THREADS / 32 * 2 * L;
-    for (int i = threadIdx.x; i < 2 * L; i += blockDim.x) {
-      double v = 0;
-      for (int g = 0; g < EBW_THREADS / 32; ++g) v += red[g * 2 * L + i];
-      row[i] = v;
-    }
-    __syncthreads();
-    lnb_emit(row, ln_g, part, accumulate, pairs, row + 2 * L);
-  }
+  if (COLS) cs.emit(reinterpret_cast<double*>(sm), ln_g, part, accumulate, pairs);
   if (npart) narrow_emit<NK>(nt, reinterpret_cast<double*>(sm), npart);
 }
 
@@ -916,8 +787,7 @@ extern "C" int pdg_edge_bwd_w2(int n_edges, const int* dst, const float* gaggr, 
   PDG_CHECK_ARG(!eu || (PDG_ALIGNED(ge_next) && a2e && a1e && st_e && (lb_e || pairs_e) &&
                         PDG_ALIGNED(a2e) && PDG_ALIGNED(a1e) && (!gz1e || PDG_ALIGNED(gz1e))),
                 "pdg_edge_bwd_w2: edge-update arguments missing or misaligned");
-  // 16-row rounds, two rounds of loads in flight (edge_bwd_w2_kernel): two buffers of images + masks
-  const size_t shm = eu ? 2 * (4 * IMG16 + 2 * MSK16) : 2 * (2 * IMG16 + MSK16);
+  const size_t shm = eu ? W2Lds<true>::total : W2Lds<false>::total;
   hipStream_t s = (hipStream_t)stream;
   if (eu)
     hipLaunchKernelGGL(edge_bwd_w2_kernel<true>, dim3(nslabs), dim3(EBW_THREADS), shm, s, dst, gaggr, ge_next, a2m,
@@ -944,11 +814,7 @@ extern "C" int pdg_edge_gout_wc(int n_edges, const float* gC, const float* e, co
   PDG_CHECK_ARG(ge_out != ge_next, "pdg_edge_gout_wc: ge_out must not alias ge_next");
   PDG_CHECK_ARG(!a2ln || (PDG_ALIGNED(a2ln) && st_ln && ln_partials), "pdg_edge_gout_wc: LayerNorm column-sum arguments");
   PDG_CHECK_ARG(!pairs || (a2ln && ln_g), "pdg_edge_gout_wc: pairs need a2ln and ln_g");
-  // LDS: two rounds' images (gC, e) + two output tiles; afterwards the slab reduction (8 KB) and the
-  // LayerNorm column sums (row groups + one row + its scratch) from 16 KB on
-  const size_t shm_pipe = 4 * IMG16 + 2 * GO_TILE * sizeof(float);
-  const size_t shm_ln = 16384 + ((size_t)EBW_THREADS / 32 + 2) * 2 * L * sizeof(double);
-  const size_t shm = shm_pipe > shm_ln ? shm_pipe : shm_ln;
+  const size_t shm = PipeLds::total;
   hipStream_t s = (hipStream_t)stream;
   dispatch_bools(
       [&](auto R, auto LNF) {
@@ -978,6 +844,11 @@ extern "C" int pdg_edge_gout_wc(int n_edges, const float* gC, const float* e, co
 // 88.9 -> 75.1 / 76.0 us per config-2 call against the earlier W2^T-product kernels, since removed; gradients
 // within 7e-8 of theirs.)
 constexpr int EEB3_BUF = 2 * IMG16 + T16;   // one round's gz2 and gz2.e images and the mask image
+struct Eeb3Lds {   // two rounds' buffers; afterwards slab_accumulate's red, then the dw0 / db0 sums of 4 wave groups
+  static constexpr size_t total = 2 * EEB3_BUF;
+  static constexpr size_t narrow = SLAB_RED_LDS, narrow_bytes = 4 * 2 * L * sizeof(double);
+  static_assert(narrow + narrow_bytes <= total, "edge_enc_bwd3's reductions inside the (dead) buffers");
+};
 // NS register sets of row loads: set s holds round n's rows (n = s mod NS) from its issue NS - 1 stages ahead
 // until its stage; the two LDS buffers alternate by round parity.  Four sets (64 KB of loads in flight per CU)
 // measured the same as two (69.7 / 70.4 vs 70.3 / 69.0 us per config-2 call): the kernel is not waiting on rows.
@@ -1112,7 +983,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void edge_enc_bwd3_kernel(
     dn[b] += __shfl_xor(dn[b], 32);
   }
   slab_accumulate(slabs + (size_t)blockIdx.x * WSLAB, accD, bsum, reinterpret_cast<float*>(sm), slab_init);
-  double* red = reinterpret_cast<double*>(sm + 16 * L * 4);   // after slab_accumulate's 8 KB
+  double* red = reinterpret_cast<double*>(sm + Eeb3Lds::narrow);   // behind slab_accumulate's red
   if (h == 0) {
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -1140,8 +1011,7 @@ extern "C" int pdg_edge_enc_bwd(int n_edges, const float* gy, const float* a2, c
   PDG_CHECK_ARG(PDG_ALIGNED(gy) && PDG_ALIGNED(a2) && PDG_ALIGNED(w0) && PDG_ALIGNED(b0) && PDG_ALIGNED(ln_g) &&
                     PDG_ALIGNED(W2T) && PDG_ALIGNED(slabs),
                 "pdg_edge_enc_bwd: misaligned pointer");
-  const size_t shm = 2 * EEB3_BUF > 16 * L * 4 + 8 * L * 8 ? 2 * EEB3_BUF : 16 * L * 4 + 8 * L * 8;
-  hipLaunchKernelGGL(edge_enc_bwd3_kernel<PDG_EEB_SETS>, dim3(nslabs), dim3(EBW_THREADS), shm, (hipStream_t)stream, gy,
+  hipLaunchKernelGGL(edge_enc_bwd3_kernel<PDG_EEB_SETS>, dim3(nslabs), dim3(EBW_THREADS), Eeb3Lds::total, (hipStream_t)stream, gy,
                      a2, e_in, w0, b0, st, lb, lb_pairs, lb_npairs, ln_g, W2T, slabs, narrow_sums, n_edges, slab_init);
   PDG_CHECK_LAUNCH("pdg_edge_enc_bwd");
   return PDG_OK;
@@ -1165,9 +1035,6 @@ extern "C" int pdg_gemm_sum2_coop(int rows, const float* in0, const float* in1, 
   PDG_CHECK_ARG(PDG_ALIGNED(in0) && PDG_ALIGNED(in1) && PDG_ALIGNED(out) && PDG_ALIGNED(W0T) && PDG_ALIGNED(W1T) &&
                     PDG_ALIGNED(res),
                 "pdg_gemm_sum2_coop: misaligned pointer");
-  // LDS: two rounds' images + two output tiles; afterwards (COLS) the row groups' sums + one row + its scratch
-  const size_t pipe = 4 * IMG16 + (size_t)2 * R16 * OT_STRIDE * sizeof(float);
-  const size_t cols = ((size_t)EBW_THREADS / 32 + 2) * 2 * L * sizeof(double);
   hipStream_t s = (hipStream_t)stream;
   PDG_CHECK_ARG(!partials || (ln_a2 && ln_st && PDG_ALIGNED(ln_a2) && (!pairs || ln_g)),
                 "pdg_gemm_sum2_coop: column partials need an aligned ln_a2, ln_st (and ln_g for pairs)");
@@ -1175,7 +1042,7 @@ extern "C" int pdg_gemm_sum2_coop(int rows, const float* in0, const float* in1, 
       [&](auto C, auto R) {
         constexpr bool COLS = decltype(C)::value;
         hipLaunchKernelGGL((gemm_sum2_coop_kernel<COLS, decltype(R)::value>), dim3(nblocks), dim3(EBW_THREADS),
-                           COLS ? (pipe > cols ? pipe : cols) : pipe, s, rows, in0, in1, W0T, W1T, res, out, ln_a2,
+                           PipeLds::total, s, rows, in0, in1, W0T, W1T, res, out, ln_a2,
                            ln_st, partials, ln_g, pairs, accumulate);
       },
       partials != nullptr, res != nullptr);
@@ -1195,15 +1062,11 @@ extern "C" int pdg_node_bwd_coop(int n_nodes, const float* gy, const float* a2n,
                     PDG_ALIGNED(Wn1aT) && PDG_ALIGNED(Wn1bT) && PDG_ALIGNED(gz2) && PDG_ALIGNED(gz1) &&
                     PDG_ALIGNED(gaggr) && PDG_ALIGNED(gx_part) && PDG_ALIGNED(ln_g),
                 "pdg_node_bwd_coop: misaligned pointer");
-  const size_t shm = 2 * EBW_IMG + EBW_MASK + (size_t)4 * EFC_TILE * sizeof(float);
-  hipLaunchKernelGGL(node_bwd_coop_kernel, dim3(nblocks), dim3(EBW_THREADS), shm, (hipStream_t)stream, n_nodes, gy,
+  hipLaunchKernelGGL(node_bwd_coop_kernel, dim3(nblocks), dim3(EBW_THREADS), NodeBwdLds::total, (hipStream_t)stream, n_nodes, gy,
                      a2n, a1n, st, lb, lb_pairs, lb_npairs, ln_g, Wn2T, Wn1aT, Wn1bT, gz2, gz1, gaggr, gx_part);
   PDG_CHECK_LAUNCH("pdg_node_bwd_coop");
   return PDG_OK;
 }
-
-// LDS of a narrow weight gradient's block reduction (narrow_emit): 16 row groups x tot doubles
-static constexpr size_t narrow_lds(int K) { return (size_t)(EBW_THREADS / 32) * (L * K + L + K) * sizeof(double); }
 
 extern "C" int pdg_mlp2_bwd_coop(int rows, const float* gy, const float* a2, const float* a1, const pdg_ln_stat* st,
                                  const pdg_ln_bwd* lb, const float* ln_g, const float* W2T, float* gz2, float* gz1,
@@ -1216,8 +1079,7 @@ extern "C" int pdg_mlp2_bwd_coop(int rows, const float* gy, const float* a2, con
                     (!gz1 || PDG_ALIGNED(gz1)) && PDG_ALIGNED(ln_g),
                 "pdg_mlp2_bwd_coop: misaligned pointer");
   PDG_CHECK_ARG(!x_narrow == !narrow_partials, "pdg_mlp2_bwd_coop: x_narrow and narrow_partials go together");
-  size_t shm = EBW_IMG + EBW_MASK + (size_t)EFC_TILE * sizeof(float);
-  if (x_narrow && narrow_lds(6) > shm) shm = narrow_lds(6);
+  const size_t shm = Mlp2BwdLds::total(x_narrow != nullptr);
   hipLaunchKernelGGL(mlp2_bwd_coop_kernel, dim3(nblocks), dim3(EBW_THREADS), shm, (hipStream_t)stream, rows, gy, a2,
                      a1, st, lb, lb_pairs, lb_npairs, ln_g, W2T, gz2, gz1, x_narrow, narrow_partials);
   PDG_CHECK_LAUNCH("pdg_mlp2_bwd_coop");
@@ -1232,11 +1094,7 @@ extern "C" int pdg_decoder_bwd_coop(int rows, const float* gy, const float* a1d,
   PDG_CHECK_ARG(gy && a1d && Wd2 && Wd1T && gz1d && gx, "pdg_decoder_bwd_coop: null argument");
   PDG_CHECK_ARG(PDG_ALIGNED(a1d) && PDG_ALIGNED(Wd2) && PDG_ALIGNED(Wd1T) && PDG_ALIGNED(gz1d) && PDG_ALIGNED(gx),
                 "pdg_decoder_bwd_coop: misaligned pointer");
-  const size_t tile = (size_t)EFC_TILE * sizeof(float);
-  const size_t cols = ((size_t)EBW_THREADS / 32 + 2) * 2 * L * sizeof(double);
-  size_t shm = EBW_IMG + tile;
-  if (partials && cols > shm) shm = cols;
-  if (narrow_partials && narrow_lds(3) > shm) shm = narrow_lds(3);
+  const size_t shm = DecBwdLds::total(partials != nullptr, narrow_partials != nullptr);
   if (partials) {
     PDG_CHECK_ARG(ln_a2 && ln_st && PDG_ALIGNED(ln_a2) && (!pairs || ln_g),
                   "pdg_decoder_bwd_coop: column partials need an aligned ln_a2, ln_st (and ln_g for pairs)");

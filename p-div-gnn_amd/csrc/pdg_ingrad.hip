@@ -40,6 +40,10 @@ __device__ __forceinline__ float row_sum32(float x) {
   return x;
 }
 
+struct GinLds {   // the gz2 image and the row tile of u; no post-loop area
+  static constexpr size_t tile = EBW_IMG, total = tile + EFC_TILE * sizeof(float);
+};
+
 // EDGE: x1 = e_in (M), w0 (128), b0 (128), perm (M); out_a = g_edge_attr (M).
 // node: x1 = a1 (M x 128), w0 = W0 (128 x 6); out_a = g_mean_stress (M x 3), out_b = g_pos (M x 2).
 template <bool EDGE>
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void enc_gin_kernel(
     const float* __restrict__ st8, int scale, float* __restrict__ out_a, float* __restrict__ out_b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   unsigned char* img2 = sm;                                    // gz2
-  float* t_u = reinterpret_cast<float*>(sm + EBW_IMG);         // u = W2^T gz2 rows
+  float* t_u = reinterpret_cast<float*>(sm + GinLds::tile);    // u = W2^T gz2 rows
   constexpr int K = EDGE ? 1 : 5, LD0 = EDGE ? 1 : 6;
   const int l = lane_id(), w = wave_id();
   const int cg = threadIdx.x & 31, rg = threadIdx.x >> 5;
@@ -110,15 +114,12 @@ __global__ __launch_bounds__(EBW_THREADS, 1) void enc_gin_kernel(
   const __amdgpu_buffer_rsrc_t rs_a = floats_rsrc(out_a, (long)M * (EDGE ? 1 : 3));
   const __amdgpu_buffer_rsrc_t rs_b = floats_rsrc(EDGE ? out_a : out_b, EDGE ? 0 : (long)M * 2);
   for (int base = r0; base < r1; base += X6_ROWS) {
-    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
     unsigned mk[2];   // [a1 > 0] of the thread's four columns, rows rg and rg + 16
     int prow[2];      // edge: the caller's edge id of those rows
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r = rg + 16 * u;
-      const bool ok = base + r < r1;
-      const f32x4 z2 = ok ? ln_relu_bwd4(pg[u], pa2[u], st, lb, g4) : zero;
-      img_store4(img2, r, cg, z2);
+      gz2_stage4<false>(img2, nullptr, base + r, r1, r, cg, pg[u], pa2[u], st, lb, g4);
       if constexpr (EDGE) {
         f32x4 a;   // encoder_kernel's a1 sign: fma(w0, e, 0) + b0 > 0 (pdg_edge_enc_bwd's)
 #pragma unroll
@@ -199,8 +200,6 @@ __global__ __launch_bounds__(1024) void graph_colsum3_kernel(const int* __restri
 // the narrow outputs are addressed with 32-bit byte offsets below DROP
 constexpr int GIN_MAX_ROWS = 1 << 26;
 
-size_t gin_lds() { return EBW_IMG + (size_t)EFC_TILE * sizeof(float); }
-
 }  // namespace
 
 extern "C" int pdg_edge_enc_gin(int n_edges, const float* gy, const float* a2, const float* e_in, const float* w0,
@@ -216,7 +215,7 @@ extern "C" int pdg_edge_enc_gin(int n_edges, const float* gy, const float* a2, c
   PDG_CHECK_ARG(!lb_pairs || lb_npairs > 0, "pdg_edge_enc_gin: lb_pairs without a count");
   PDG_CHECK_ARG(PDG_ALIGNED(gy) && PDG_ALIGNED(a2) && PDG_ALIGNED(ln_g) && PDG_ALIGNED(W2T),
                 "pdg_edge_enc_gin: misaligned pointer");
-  hipLaunchKernelGGL(enc_gin_kernel<true>, dim3(nblocks), dim3(EBW_THREADS), gin_lds(), (hipStream_t)stream, n_edges,
+  hipLaunchKernelGGL(enc_gin_kernel<true>, dim3(nblocks), dim3(EBW_THREADS), GinLds::total, (hipStream_t)stream, n_edges,
                      gy, a2, e_in, w0, b0, st, lb, lb_pairs, lb_npairs, ln_g, W2T, perm, stats8, scale_input,
                      g_edge_attr, (float*)nullptr);
   PDG_CHECK_LAUNCH("pdg_edge_enc_gin");
@@ -235,7 +234,7 @@ extern "C" int pdg_node_enc_gin(int n_nodes, const float* gy, const float* a2, c
   PDG_CHECK_ARG(!lb_pairs || lb_npairs > 0, "pdg_node_enc_gin: lb_pairs without a count");
   PDG_CHECK_ARG(PDG_ALIGNED(gy) && PDG_ALIGNED(a2) && PDG_ALIGNED(a1) && PDG_ALIGNED(ln_g) && PDG_ALIGNED(W2T),
                 "pdg_node_enc_gin: misaligned pointer");
-  hipLaunchKernelGGL(enc_gin_kernel<false>, dim3(nblocks), dim3(EBW_THREADS), gin_lds(), (hipStream_t)stream, n_nodes,
+  hipLaunchKernelGGL(enc_gin_kernel<false>, dim3(nblocks), dim3(EBW_THREADS), GinLds::total, (hipStream_t)stream, n_nodes,
                      gy, a2, a1, W0, (const float*)nullptr, st, lb, lb_pairs, lb_npairs, ln_g, W2T,
                      (const int*)nullptr, stats8, scale_input, g_mean_stress, g_pos);
   PDG_CHECK_LAUNCH("pdg_node_enc_gin");

@@ -11,20 +11,11 @@
 // B = X (i on the lane, k = lane half): both operands are plain 128-byte
 // row segments, read straight from global memory.  4 waves per block, wave w
 // owns outputs o in [32w, 32w+32) and all 128 inputs (4 accumulators).
-#include "pdg_common.hpp"
-#include "pdg_runtime.hpp"
-#include "pdg_x6.hpp"
+#include "pdg_coop.hpp"
 
 using namespace pdg;
 
 constexpr int SLAB = L * L + L;   // floats per slab
-
-__device__ __forceinline__ void zero_acc16(f32x16 (&acc)[4]) {
-#pragma unroll
-  for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-}
 
 __device__ __forceinline__ void wgrad_pass(int M, int r0, int r1, const float* __restrict__ G,
                                            const float* __restrict__ X, f32x16 (&acc)[4], double& bsum) {
@@ -74,7 +65,7 @@ __global__ __launch_bounds__(256) void wgrad_accum_kernel(int M, const float* __
   const int r0 = (int)min((long)M, chunk * blockIdx.x);
   const int r1 = (int)min((long)M, chunk * (blockIdx.x + 1));
   f32x16 acc[4];
-  zero_acc16(acc);
+  zero_acc(acc);
   double bsum = 0;
   wgrad_pass(M, r0, r1, G, X, acc, bsum);
   if (G2) wgrad_pass(M, r0, r1, G2, X2, acc, bsum);
@@ -235,14 +226,7 @@ __global__ __launch_bounds__(256) void wgrad_narrow_kernel(int M, const float* _
     float nv[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) nv[i] = narrow[(size_t)k * K + i];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-#pragma unroll
-      for (int i = 0; i < K; ++i) acc[c * K + i] += (double)(w[c] * nv[i]);
-      acc[4 * K + c] += (double)w[c];
-    }
-#pragma unroll
-    for (int i = 0; i < K; ++i) acc[4 * K + 4 + i] += (double)nv[i];
+    narrow_add<K>(acc, w, nv);
   }
 #pragma unroll
   for (int p = 0; p < NP; ++p) red[hw][j][p] = acc[p];
