@@ -23,7 +23,9 @@
 #include <stdint.h>
 
 #include "pdg_common.hpp"
+#include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
+#include "pdg_sym3.hpp"
 
 using namespace pdg;
 
@@ -33,70 +35,6 @@ constexpr int BD_T = 1024;      // threads per graph of boundary_residuals_kerne
 constexpr int BD_COLS = 9;      // table columns
 constexpr int BD_CT = 256;      // threads per block of boundary_residuals_bwd_kernel
 constexpr int BD_CHUNKS = 16;   // its blocks per graph
-
-// pdg_criteria.hip's cr_block_sum: K doubles summed over the block at once; valid in every thread.  `red` holds
-// K * 16 doubles.
-template <int K>
-__device__ __forceinline__ void bd_block_sum(double (&x)[K], double* red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = wave_sum(x[k]);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k * 16 + w] = x[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = 0;
-    for (int i = 0; i < nw; ++i) s += red[k * 16 + i];
-    x[k] = s;
-  }
-}
-
-// (v, i) <- the better of (v, i) and (ov, oi): the larger value, the lower index on equal values.  Commutative
-// and associative, so the block's result does not depend on the folding order.
-__device__ __forceinline__ void better(double& v, int& i, double ov, int oi) {
-  if (ov > v || (ov == v && oi < i)) {
-    v = ov;
-    i = oi;
-  }
-}
-
-// pdg_criteria.hip's cr_block_best: the block's best (value, index); valid in every thread.
-__device__ __forceinline__ void bd_block_best(double& v, int& i, double* rv, int* ri) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(i, o);
-    better(v, i, ov, oi);
-  }
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0) {
-    rv[w] = v;
-    ri[w] = i;
-  }
-  __syncthreads();
-  v = rv[0];
-  i = ri[0];
-  for (int k = 1; k < nw; ++k) better(v, i, rv[k], ri[k]);
-}
-
-struct Row {
-  double x, y, xy;
-};
-
-__device__ __forceinline__ Row load_row(const float* __restrict__ sig, int i) {
-  return Row{(double)sig[(size_t)i * 3], (double)sig[(size_t)i * 3 + 1], (double)sig[(size_t)i * 3 + 2]};
-}
-
-// f = sigma . m: fx = sxx mx + sxy my, fy = sxy mx + syy my (the products of two fp32 values are exact in fp64).
-__device__ __forceinline__ void force(const Row& s, double mx, double my, double& fx, double& fy) {
-#pragma clang fp contract(off)
-  fx = s.x * mx + s.xy * my;
-  fy = s.xy * mx + s.y * my;
-}
 
 // A node takes part in the traction sums iff its label is +-1 and its boundary length is > 0 (false for NaN).
 __device__ __forceinline__ bool takes_part(int64_t label, float bl) { return (label == 1 || label == -1) && bl > 0.f; }
@@ -125,7 +63,7 @@ __global__ __launch_bounds__(BD_T) void boundary_residuals_kernel(
   double best = -1.0;   // every |f| / blen is >= 0
   int besti = INT_MAX;
   for (int i = n0 + (int)threadIdx.x; i < n1; i += BD_T) {
-    const Row a = load_row(sig, i);
+    const Sym3 a = load_row(sig, i);
     const int64_t lab = labels[i];
     const float bl = blen[i];
     if (takes_part(lab, bl)) {
@@ -150,19 +88,19 @@ __global__ __launch_bounds__(BD_T) void boundary_residuals_kernel(
       }
     }
     if (rowptr) {
-      for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-        if (eattr[perm[k]] != 0.f) continue;   // a periodic connection has length exactly 0
+      for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {   // the periodic connections of i (pdg_sym3.hpp)
+        if (eattr[perm[k]] != 0.f) continue;
         const int j = src[k];
-        if (j < n0 || j >= n1) continue;       // an edge never leaves its graph; one that does is not read
-        const Row b = load_row(sig, j);
+        if (j < n0 || j >= n1) continue;
+        const Sym3 b = load_row(sig, j);
         const double dx = a.x - b.x, dy = a.y - b.y, dxy = a.xy - b.xy;
         s[7] += dx * dx + dy * dy + dxy * dxy;
         s[8] += 1.0;
       }
     }
   }
-  bd_block_sum<10>(s, red);
-  bd_block_best(best, besti, redv, redi);
+  block_sum_k<10>(s, red);
+  block_best(best, besti, redv, redi);
   if (threadIdx.x == 0) {
     double* row = table + (size_t)g * BD_COLS;
 #pragma unroll
@@ -189,26 +127,19 @@ __global__ __launch_bounds__(BD_CT) void boundary_residuals_bwd_kernel(
   const double ct = gt == 0.0 ? 0.0 : (L > 0.0 ? gt / L : (double)NAN);
   const double cp = gp == 0.0 ? 0.0 : (np > 0.0 ? gp / np : (double)NAN);
   for (int i = n0 + chunk * BD_CT + (int)threadIdx.x; i < n1; i += BD_CHUNKS * BD_CT) {
-    const Row a = load_row(sig, i);
+    const Sym3 a = load_row(sig, i);
     double o[3] = {0.0, 0.0, 0.0};   // a row that takes no part: exact zeros
     const float bl = blen[i];
-    if (ct != 0.0 && labels[i] == -1 && bl > 0.f) {
-      const double mx = (double)bvec[(size_t)i * 2], my = (double)bvec[(size_t)i * 2 + 1];
-      double fx, fy;
-      force(a, mx, my, fx, fy);
-      const double c = 2.0 / (double)bl;
-      o[0] = ct * (c * (fx * mx));
-      o[1] = ct * (c * (fy * my));
-      o[2] = ct * (c * (fx * my + fy * mx));
-    }
+    if (ct != 0.0 && labels[i] == -1 && bl > 0.f)
+      traction_grad(a, (double)bvec[(size_t)i * 2], (double)bvec[(size_t)i * 2 + 1], bl, ct, o);
     if (cp != 0.0 && rowptr) {
       double d[3] = {0.0, 0.0, 0.0};
       int cnt = 0;
-      for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {   // the periodic connections of i (pdg_sym3.hpp)
         if (eattr[perm[k]] != 0.f) continue;
         const int j = src[k];
         if (j < n0 || j >= n1) continue;
-        const Row b = load_row(sig, j);
+        const Sym3 b = load_row(sig, j);
         d[0] += a.x - b.x;
         d[1] += a.y - b.y;
         d[2] += a.xy - b.xy;
@@ -223,11 +154,6 @@ __global__ __launch_bounds__(BD_CT) void boundary_residuals_bwd_kernel(
   }
 }
 
-bool edges_all_or_none(const int* rowptr, const int* src, const int* perm, const float* eattr) {
-  const int given = (rowptr != nullptr) + (src != nullptr) + (perm != nullptr) + (eattr != nullptr);
-  return given == 0 || given == 4;
-}
-
 }  // namespace
 
 extern "C" int pdg_boundary_residuals(int n_graphs, const int* ptr, const float* sigma, const float* bvec,
@@ -237,7 +163,7 @@ extern "C" int pdg_boundary_residuals(int n_graphs, const int* ptr, const float*
   PDG_CHECK_ARG(n_graphs > 0, "pdg_boundary_residuals: bad sizes (n_graphs > 0)");
   PDG_CHECK_ARG(ptr && sigma && bvec && blen && labels && table && argmax,
                 "pdg_boundary_residuals: null argument (ptr, sigma, bvec, blen, labels, table and argmax are required)");
-  PDG_CHECK_ARG(edges_all_or_none(rowptr_dst, src, perm, edge_attr),
+  PDG_CHECK_ARG(all_or_none({rowptr_dst, src, perm, edge_attr}),
                 "pdg_boundary_residuals: partial edge arguments (rowptr_dst, src, perm and edge_attr are given "
                 "together or all NULL)");
   hipLaunchKernelGGL(boundary_residuals_kernel, dim3(n_graphs), dim3(BD_T), 0, (hipStream_t)stream, ptr, sigma, bvec,
@@ -255,7 +181,7 @@ extern "C" int pdg_boundary_residuals_bwd(int n_graphs, const int* ptr, const fl
   PDG_CHECK_ARG(ptr && sigma && bvec && blen && labels && table && out,
                 "pdg_boundary_residuals_bwd: null argument (ptr, sigma, bvec, blen, labels, table and out are "
                 "required)");
-  PDG_CHECK_ARG(edges_all_or_none(rowptr_dst, src, perm, edge_attr),
+  PDG_CHECK_ARG(all_or_none({rowptr_dst, src, perm, edge_attr}),
                 "pdg_boundary_residuals_bwd: partial edge arguments (rowptr_dst, src, perm and edge_attr are given "
                 "together or all NULL)");
   hipLaunchKernelGGL(boundary_residuals_bwd_kernel, dim3(n_graphs * BD_CHUNKS), dim3(BD_CT), 0, (hipStream_t)stream,

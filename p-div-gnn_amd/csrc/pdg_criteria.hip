@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "pdg_common.hpp"
+#include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
 
 using namespace pdg;
@@ -30,55 +31,6 @@ constexpr int CR_T = 1024;   // threads per graph
 // registers between the forward's two passes; rows beyond are read and evaluated again.  The same values and
 // sums in the same order either way.
 constexpr int CR_C = 4;
-
-// pdg_metrics.hip's ev_block_sum: K doubles summed over the block at once; valid in every thread.  `red` holds
-// K * 16 doubles.
-template <int K>
-__device__ __forceinline__ void cr_block_sum(double (&x)[K], double* red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = wave_sum(x[k]);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k * 16 + w] = x[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = 0;
-    for (int i = 0; i < nw; ++i) s += red[k * 16 + i];
-    x[k] = s;
-  }
-}
-
-// (v, i) <- the better of (v, i) and (ov, oi): the larger value, the lower index on equal values.  Commutative
-// and associative, so the block's result does not depend on the folding order.
-__device__ __forceinline__ void better(double& v, int& i, double ov, int oi) {
-  if (ov > v || (ov == v && oi < i)) {
-    v = ov;
-    i = oi;
-  }
-}
-
-// The block's best (value, index); valid in every thread.  `rv` / `ri` hold 16 entries each.
-__device__ __forceinline__ void cr_block_best(double& v, int& i, double* rv, int* ri) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(i, o);
-    better(v, i, ov, oi);
-  }
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0) {
-    rv[w] = v;
-    ri[w] = i;
-  }
-  __syncthreads();
-  v = rv[0];
-  i = ri[0];
-  for (int k = 1; k < nw; ++k) better(v, i, rv[k], ri[k]);
-}
 
 struct Crit {
   double vm, s1, s2, d, r, c;   // von Mises, principal stresses, (sx - sy) / 2, in-plane maximum shear, criterion
@@ -217,8 +169,8 @@ __global__ __launch_bounds__(CR_T) void stress_criteria_kernel(const int* __rest
     float wp;
     visit(i, c, wp);
   }
-  cr_block_sum<3>(s, red);
-  cr_block_best(best, besti, redv, redi);
+  block_sum_k<3>(s, red);
+  block_best(best, besti, redv, redi);
   if (s[2] > 0.0 || besti == INT_MAX) {   // a NaN criterion, or no participating node (uniform: no barrier skipped)
     if (threadIdx.x < 4) table[(size_t)g * 4 + threadIdx.x] = NAN;
     if (threadIdx.x == 0) argmax[g] = -1;
@@ -242,7 +194,7 @@ __global__ __launch_bounds__(CR_T) void stress_criteria_kernel(const int* __rest
     const Crit q = crit_eval((double)sig[(size_t)i * 3], (double)sig[(size_t)i * 3 + 1], (double)sig[(size_t)i * 3 + 2], crit);
     acc(q.c, w);
   }
-  cr_block_sum<2>(t, red);
+  block_sum_k<2>(t, red);
   if (threadIdx.x == 0) {
     double* row = table + (size_t)g * 4;
     const double W = s[0];
@@ -282,7 +234,7 @@ __global__ __launch_bounds__(CR_T) void stress_criteria_bwd_kernel(const int* __
         s[1] += (double)w * exp(rho * (q.c - M));
       }
     }
-    cr_block_sum<2>(s, red);
+    block_sum_k<2>(s, red);
   }
   for (int i = n0 + (int)threadIdx.x; i < n1; i += CR_T) {
     const float w = wts ? wts[i] : 1.f;

@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "pdg_common.hpp"
+#include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
 
 using namespace pdg;
@@ -28,18 +29,6 @@ namespace {
 
 constexpr int EQ_T = 1024;            // threads per graph
 constexpr int EQ_FLOATS = 11;         // scratch floats per node: lam, r, p, sp (2 each) and work (3)
-
-// The block's sum of x, folded in a fixed order and valid in every thread.  `red` holds 16 doubles.
-__device__ __forceinline__ double eq_block_sum(double x, double* red) {
-  x = wave_sum(x);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0) red[w] = x;
-  __syncthreads();
-  double s = 0;
-  for (int i = 0; i < nw; ++i) s += red[i];
-  return s;
-}
 
 struct Op {
   const int* arp;
@@ -157,7 +146,7 @@ __global__ __launch_bounds__(EQ_T) void equilibrate_kernel(
     r[k + 1] = p[k + 1] = (float)d1;
     s += d0 * d0 + d1 * d1;
   }
-  double rr = eq_block_sum(s, red);
+  double rr = block_sum(s, red);
   const double bnorm = sqrt(rr);
   if (rr == 0.0) {   // nothing to remove: no interior node, no operator entry, or a field C annihilates
     for (size_t e = e0 + tid; e < e1; e += EQ_T) out[e] = in[e];
@@ -190,7 +179,7 @@ __global__ __launch_bounds__(EQ_T) void equilibrate_kernel(
       sp[k + 1] = q1;
       s += (double)p[k] * (double)q0 + (double)p[k + 1] * (double)q1;
     }
-    const double pSp = eq_block_sum(s, red);
+    const double pSp = block_sum(s, red);
     if (!(pSp > 0.0)) break;   // breakdown (p in the null space of C^T, or a non-finite input)
     const double alpha = rr / pSp;
     s = 0;
@@ -205,7 +194,7 @@ __global__ __launch_bounds__(EQ_T) void equilibrate_kernel(
         s += (double)ri * (double)ri;
       }
     }
-    const double rrn = eq_block_sum(s, red);
+    const double rrn = block_sum(s, red);
     const double beta = rrn / rr;
     rr = rrn;
     res = sqrt(rr);
@@ -239,7 +228,7 @@ __global__ __launch_bounds__(EQ_T) void equilibrate_kernel(
     row_apply(o, v, out, tr, d0, d1);
     s += d0 * d0 + d1 * d1;
   }
-  const double tres = sqrt(eq_block_sum(s, red));
+  const double tres = sqrt(block_sum(s, red));
   if (tid == 0) {
     row[0] = bnorm;
     row[1] = tres;

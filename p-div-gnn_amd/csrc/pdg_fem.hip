@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "pdg_common.hpp"
+#include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
 
 using namespace pdg;
@@ -41,26 +42,6 @@ struct Material {
 __host__ __device__ inline Material material(double young, double poisson) {
   const double c11 = young / (1.0 - poisson * poisson);
   return Material{c11, poisson * c11, c11 * (1.0 - poisson) / 2.0};
-}
-
-// The block's sums of K values, folded in a fixed order and valid in every thread.  `red` holds 16 K doubles.
-template <int K>
-__device__ __forceinline__ void block_sums(double (&x)[K], double* red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = wave_sum(x[k]);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[w * K + k] = x[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = 0;
-  for (int i = 0; i < nw; ++i) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) x[k] += red[i * K + k];
-  }
 }
 
 // ------------------------------------------------------------------------------------------------ element table
@@ -272,9 +253,9 @@ __global__ __launch_bounds__(FEM_T) void fem_solve_kernel(
     babs2 += abx * abx + aby * aby;
     nact += act ? 1.0 : 0.0;
   }
-  block_sums(s, red);
+  block_sum_k_wave_major(s, red);
   double t2[2] = {babs2, nact};
-  block_sums(t2, red);
+  block_sum_k_wave_major(t2, red);
   const double bnorm = sqrt(s[0]), babs = sqrt(t2[0]);
   nact = t2[1];
 
@@ -319,7 +300,7 @@ __global__ __launch_bounds__(FEM_T) void fem_solve_kernel(
       ap[k + 1] = ay;
       q[0] += p[k] * ax + p[k + 1] * ay;
     }
-    block_sums(q, red);
+    block_sum_k_wave_major(q, red);
     const double pAp = q[0];
     if (!(pAp > 0.0) || !(pAp < INFINITY) || !(rz < INFINITY) || !(rz > -INFINITY)) {
       status = ST_BREAKDOWN;
@@ -344,7 +325,7 @@ __global__ __launch_bounds__(FEM_T) void fem_solve_kernel(
       s[4] += rx;
       s[5] += ry;
     }
-    block_sums(s, red);
+    block_sum_k_wave_major(s, red);
     ++it;
     res = sqrt(s[0]);
     if (!(s[0] < INFINITY)) {   // a non-finite residual (NaN included)
@@ -373,7 +354,7 @@ __global__ __launch_bounds__(FEM_T) void fem_solve_kernel(
     mu[0] += x[k];
     mu[1] += x[k + 1];
   }
-  block_sums(mu, red);
+  block_sum_k_wave_major(mu, red);
   for (int v = n0 + tid; v < n1; v += FEM_T) {
     const size_t k = (size_t)v * 2;
     if (!(dinv[k] > 0.0)) continue;
@@ -395,7 +376,7 @@ __global__ __launch_bounds__(FEM_T) void fem_solve_kernel(
     apply_row(m, mt, v, x, ax, ay);
     tr[0] += (bx - ax) * (bx - ax) + (by - ay) * (by - ay);
   }
-  block_sums(tr, red);
+  block_sum_k_wave_major(tr, red);
   if (tid == 0) {
     row[0] = (double)it;
     row[1] = bnorm;
@@ -422,17 +403,6 @@ __device__ __forceinline__ bool element_fields(const float* points, int dim, int
   strain_of(elem + (size_t)f * FEM_ELEM, ux, uy, ep);
   stress_of(mt, ep, sg);
   return true;
-}
-
-// The graph of node v: the last g with ptr[g] <= v.
-__device__ __forceinline__ int graph_of(const int* ptr, int n_graphs, int v) {
-  int lo = 0, hi = n_graphs;   // ptr[lo] <= v < ptr[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= v) lo = mid;
-    else hi = mid;
-  }
-  return lo;
 }
 
 __global__ __launch_bounds__(256) void fem_nodal_kernel(
@@ -514,7 +484,7 @@ __global__ __launch_bounds__(FEM_T) void fem_sums_kernel(
     }
     s[6] += area;
   }
-  block_sums(s, red);
+  block_sum_k_wave_major(s, red);
   float lo_x = INFINITY, hi_x = -INFINITY, lo_y = INFINITY, hi_y = -INFINITY;
   for (int v = n0 + tid; v < n1; v += FEM_T) {
     const float x = points[(size_t)v * dim], y = points[(size_t)v * dim + 1];

@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "pdg_common.hpp"
+#include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
 
 using namespace pdg;
@@ -25,26 +26,6 @@ constexpr int HM_T = 1024;     // threads per graph of graph_wmean_kernel
 constexpr int HM_MAXC = 9;     // most columns of a field (the localisation tensor's 3 x 3)
 constexpr int HM_CT = 256;     // threads per block of mean_correct_kernel
 constexpr int HM_CHUNKS = 16;  // its blocks per graph
-
-// pdg_criteria.hip's cr_block_sum: K doubles summed over the block at once; valid in every thread.  `red` holds
-// K * 16 doubles.
-template <int K>
-__device__ __forceinline__ void hm_block_sum(double (&x)[K], double* red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = wave_sum(x[k]);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k * 16 + w] = x[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = 0;
-    for (int i = 0; i < nw; ++i) s += red[k * 16 + i];
-    x[k] = s;
-  }
-}
 
 // table[g] = (W, S_0 .. S_{C-1}).  A graph without rows, or without a participating one, gets zeros.
 template <int C>
@@ -64,7 +45,7 @@ __global__ __launch_bounds__(HM_T) void graph_wmean_kernel(const int* __restrict
 #pragma unroll
     for (int c = 0; c < C; ++c) s[1 + c] += (double)w * (double)rows[(size_t)i * C + c];
   }
-  hm_block_sum<C + 1>(s, red);
+  block_sum_k<C + 1>(s, red);
   if (threadIdx.x == 0)
 #pragma unroll
     for (int k = 0; k <= C; ++k) table[(size_t)g * (C + 1) + k] = s[k];

@@ -7,41 +7,12 @@
 // The divergence operator is applied sparsely (CSR, ~14 nnz per row) instead
 // of the reference's dense `to_dense()[:, :2N]` (8*N^2 bytes per graph).
 #include "pdg_common.hpp"
+#include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
 
 using namespace pdg;
 
-__device__ __forceinline__ double block_sum(double x, double* red) {
-  x = wave_sum(x);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0) red[w] = x;
-  __syncthreads();
-  double s = 0;
-  for (int i = 0; i < nw; ++i) s += red[i];
-  return s;  // valid in every thread
-}
-
 // ============================================================================ NMSE
-// K doubles summed over the block at once (one LDS round instead of K); valid in every thread.
-template <int K>
-__device__ __forceinline__ void block_sum_k(double (&x)[K], double* red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = wave_sum(x[k]);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k * 16 + w] = x[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = 0;
-    for (int i = 0; i < nw; ++i) s += red[k * 16 + i];
-    x[k] = s;
-  }
-}
-
 // One block of 1024 threads per graph; the three channels in one pass over the graph's nodes
 // (loads of NF_U nodes issued together): a 256-thread block with one channel per pass and a
 // reduction per channel ran 31 us for 8 graphs of 5,041 nodes (latency-bound).  The first NF_C
@@ -182,15 +153,6 @@ extern "C" int pdg_nmse_fwd_bwd(int n_graphs, const int* ptr, const float* gt, c
                      scale, accumulate, g_pred);
   PDG_CHECK_LAUNCH("pdg_nmse_fwd_bwd");
   return PDG_OK;
-}
-
-__device__ __forceinline__ int graph_of(const int* __restrict__ ptr, int B, int node) {
-  int lo = 0, hi = B;  // ptr[lo] <= node < ptr[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= node) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 // d loss_g / d pred[n][c] = (1/3) * (-2) (gt - pred) / den_c ; times the upstream scale.

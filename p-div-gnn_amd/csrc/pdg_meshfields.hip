@@ -52,6 +52,7 @@
 #include <algorithm>
 
 #include "pdg_bbox.hpp"
+#include "pdg_cell.hpp"
 #include "pdg_group.hpp"
 #include "pdg_runtime.hpp"
 #include "pdg_scan.hpp"
@@ -165,14 +166,6 @@ bool sizes_ok(int n_nodes, int n_faces, int nv) {
   // the scan indexes base + i < n + SCAN_BLOCK in int32; an item position (< nv^2 F) fills a slot's low word
   return (nv == 3 || nv == 4) && n_nodes > 0 && n_faces >= 0 && (long)n_nodes + SCAN_BLOCK < 0x7fffffffL &&
          (long)(nv * nv) * n_faces + SCAN_BLOCK < 0x7fffffffL;
-}
-
-template <int NV>
-__device__ __forceinline__ bool in_range(const int64_t* __restrict__ t, int n) {
-  bool ok = true;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) ok = ok && t[v] >= 0 && t[v] < n;
-  return ok;
 }
 
 // The vertex after / before vertex v in the face's own cyclic order.
@@ -349,11 +342,6 @@ __global__ __launch_bounds__(PT) void labels_kernel(int n, const int* __restrict
 }
 
 // --------------------------------------------------------------------------------- operator
-template <int NV>
-struct Cell {
-  double x[NV], y[NV], det;
-};
-
 // A vertex's coordinate by a run-time index: selects over registers (the loops are unrolled), no indexed array.
 template <int NV>
 __device__ __forceinline__ double pick(const double (&a)[NV], unsigned k) {
@@ -361,30 +349,6 @@ __device__ __forceinline__ double pick(const double (&a)[NV], unsigned k) {
 #pragma unroll
   for (int v = 1; v < NV; ++v) r = k == (unsigned)v ? a[v] : r;
   return r;
-}
-
-// meshgen.p1_divergence_operator's / q1_divergence_operator's fp64 expressions, one rounding per operation.
-// det = 2 * signed area: (xb - xa)(yc - ya) - (xc - xa)(yb - ya) of a triangle, the diagonals' cross product
-// (xc - xa)(yd - yb) - (xd - xb)(yc - ya) of a quad.
-template <int NV>
-__device__ __forceinline__ Cell<NV> cell(const float* __restrict__ p, int dim, const int64_t* __restrict__ t) {
-#pragma clang fp contract(off)
-  Cell<NV> q;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    q.x[v] = p[(size_t)t[v] * dim];
-    q.y[v] = p[(size_t)t[v] * dim + 1];
-  }
-  if constexpr (NV == 3) {
-    const double m0 = (q.x[1] - q.x[0]) * (q.y[2] - q.y[0]);
-    const double m1 = (q.x[2] - q.x[0]) * (q.y[1] - q.y[0]);
-    q.det = m0 - m1;
-  } else {
-    const double m0 = (q.x[2] - q.x[0]) * (q.y[3] - q.y[1]);
-    const double m1 = (q.x[3] - q.x[1]) * (q.y[2] - q.y[0]);
-    q.det = m0 - m1;
-  }
-  return q;
 }
 
 template <int NV>
@@ -397,7 +361,7 @@ __global__ __launch_bounds__(PT) void div_face_kernel(int nf, const int64_t* __r
     int ok = in_range<NV>(t, n);
     if (!ok) {
       bad |= DV_RANGE;
-    } else if (cell<NV>(p, dim, t).det == 0.0) {
+    } else if (cell_of<NV>(p, dim, t).det == 0.0) {
       bad |= DV_DEGENERATE;
       ok = 0;
     }
@@ -453,7 +417,7 @@ __global__ __launch_bounds__(PT) void div_emit_kernel(int n, const float* __rest
     for (int k = b; k < e; ++k) {
       const unsigned id = (unsigned)(sorted[k] & 0xffffffffu);
       const unsigned f = id / (NV * NV), q = id - NV * NV * f;
-      if (q / NV == q % NV) wsum += 0.5 * fabs(cell<NV>(p, dim, faces + NV * (size_t)f).det);
+      if (q / NV == q % NV) wsum += 0.5 * fabs(cell_of<NV>(p, dim, faces + NV * (size_t)f).det);
     }
     const long o = 2L * uptr[r];
     int j = 0;
@@ -463,7 +427,7 @@ __global__ __launch_bounds__(PT) void div_emit_kernel(int n, const float* __rest
       for (; k < e && (unsigned)(sorted[k] >> 32) == c; ++k) {
         const unsigned id = (unsigned)(sorted[k] & 0xffffffffu);
         const unsigned f = id / (NV * NV), vn = (id - NV * NV * f) % NV;
-        const Cell<NV> t = cell<NV>(p, dim, faces + NV * (size_t)f);
+        const Cell<NV> t = cell_of<NV>(p, dim, faces + NV * (size_t)f);
         const double area = 0.5 * fabs(t.det);
         // area * g[vn] = the integral of grad N_vn over the face: (y[vn + 1] - y[vn - 1], x[vn - 1] - x[vn + 1]) / 2,
         // the P1 gradient of a triangle and the mean Q1 gradient of a quad
@@ -545,7 +509,7 @@ __global__ __launch_bounds__(PT) void area_emit_kernel(int n, const float* __res
     double a = 0.0;
     for (int k = b; k < e; ++k) {
       const unsigned f = (unsigned)(sorted[k] >> 32);
-      const Cell<NV> t = cell<NV>(p, dim, faces + NV * (size_t)f);
+      const Cell<NV> t = cell_of<NV>(p, dim, faces + NV * (size_t)f);
       if constexpr (NV == 3) {
         a += 0.5 * fabs(t.det) / 3.0;
       } else {
@@ -625,7 +589,7 @@ __global__ __launch_bounds__(PT) void bvec_emit_kernel(int n, const float* __res
       const double xc = p[ic * dim], yc = p[ic * dim + 1];
       double rx = yb - ya, ry = -(xb - xa);
       sl += sqrt(rx * rx + ry * ry);
-      if (cell<NV>(p, dim, t).det == 0.0) {
+      if (cell_of<NV>(p, dim, t).det == 0.0) {
         bad |= BV_FLAT;
         continue;
       }

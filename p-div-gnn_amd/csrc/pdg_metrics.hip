@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "pdg_common.hpp"
+#include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
 
 using namespace pdg;
@@ -18,25 +19,6 @@ using namespace pdg;
 namespace {
 
 constexpr int EV_T = 1024;   // threads per graph
-
-// K doubles summed over the block at once; valid in every thread.  `red` holds K * 16 doubles.
-template <int K>
-__device__ __forceinline__ void ev_block_sum(double (&x)[K], double* red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = wave_sum(x[k]);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k * 16 + w] = x[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = 0;
-    for (int i = 0; i < nw; ++i) s += red[k * 16 + i];
-    x[k] = s;
-  }
-}
 
 // compare_results.py:713-726 in fp64.
 __device__ __forceinline__ double von_mises(double x, double y, double xy) {
@@ -95,7 +77,7 @@ __global__ __launch_bounds__(EV_T) void eval_nmse_kernel(const int* __restrict__
   for (int k = 0; k < EV_C; ++k)
     if (first + k * EV_T < n1) acc_mean(c[k]);
   for (int i = rest; i < n1; i += EV_T) acc_mean(load_node(gt, pred, i));
-  ev_block_sum<4>(m, red);
+  block_sum_k<4>(m, red);
 #pragma unroll
   for (int k = 0; k < 4; ++k) m[k] /= n;   // gt.mean(axis=0)
 
@@ -123,7 +105,7 @@ __global__ __launch_bounds__(EV_T) void eval_nmse_kernel(const int* __restrict__
   for (int k = 0; k < EV_C; ++k)
     if (first + k * EV_T < n1) acc_sums(c[k], first + k * EV_T);
   for (int i = rest; i < n1; i += EV_T) acc_sums(load_node(gt, pred, i), i);
-  ev_block_sum<8>(s, red);
+  block_sum_k<8>(s, red);
 
   if (threadIdx.x == 0) {
     double* row = table + (size_t)g * 6;
@@ -209,7 +191,7 @@ __global__ __launch_bounds__(EV_T) void eval_div_kernel(const int* __restrict__ 
       s[3] += rabs ? fabs(e1) : e1 * e1;
     }
   }
-  ev_block_sum<4>(s, red);
+  block_sum_k<4>(s, red);
   if (threadIdx.x == 0) {
     const double nn = (double)n;
     table[(size_t)g * 2] = s[0] / nn + s[1] / nn;       // mean over all n_g rows, summed over x and y

@@ -16,15 +16,16 @@
 //
 // pdg_phys_loss_bwd: node-parallel; a row depends on its own inputs, its neighbours' y and its graph's table row.
 //
-// The per-node formulas and the block sum restate pdg_boundary.hip's and pdg_homog.hip's (they live in those
-// files' unnamed namespaces; moving them would have to be shown not to change those kernels' code).  Every
-// per-node formula is compiled without contraction into fused multiply-adds, so the forward, the backward and
-// the host restatement form the same fp64 values.
+// The per-node formulas are pdg_boundary.hip's (pdg_sym3.hpp) and the block sum is every per-graph kernel's
+// (pdg_reduce.hpp).  Every per-node formula is compiled without contraction into fused multiply-adds, so the
+// forward, the backward and the host restatement form the same fp64 values.
 #include <math.h>
 #include <stdint.h>
 
 #include "pdg_common.hpp"
+#include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
+#include "pdg_sym3.hpp"
 
 using namespace pdg;
 
@@ -37,41 +38,10 @@ constexpr int PL_CT = 256;    // threads per block of phys_loss_bwd_kernel
 // table columns
 enum { C_L = 0, C_T2, C_P2, C_NP, C_W, C_SXX, C_SYY, C_SXY, C_D, C_LT, C_LP, C_LM };
 
-// pdg_criteria.hip's cr_block_sum: K doubles summed over the block at once; valid in every thread.  `red` holds
-// K * 16 doubles.
-template <int K>
-__device__ __forceinline__ void pl_block_sum(double (&x)[K], double* red) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = wave_sum(x[k]);
-  const int w = wave_id(), nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[k * 16 + w] = x[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = 0;
-    for (int i = 0; i < nw; ++i) s += red[k * 16 + i];
-    x[k] = s;
-  }
-}
-
-struct Row {
-  double x, y, xy;
-};
-
 // z = y + mean / std, one fp64 addition per component
-__device__ __forceinline__ Row load_z(const float* __restrict__ y, int i, double off) {
+__device__ __forceinline__ Sym3 load_z(const float* __restrict__ y, int i, double off) {
 #pragma clang fp contract(off)
-  return Row{(double)y[(size_t)i * 3] + off, (double)y[(size_t)i * 3 + 1] + off, (double)y[(size_t)i * 3 + 2] + off};
-}
-
-// f = z . m: fx = zxx mx + zxy my, fy = zxy mx + zyy my
-__device__ __forceinline__ void force(const Row& s, double mx, double my, double& fx, double& fy) {
-#pragma clang fp contract(off)
-  fx = s.x * mx + s.xy * my;
-  fy = s.xy * mx + s.y * my;
+  return Sym3{(double)y[(size_t)i * 3] + off, (double)y[(size_t)i * 3 + 1] + off, (double)y[(size_t)i * 3 + 2] + off};
 }
 
 // Sums s[0..7]: L_int, T2, the jump sum and the edge count (both halved at the end), W, S_xx, S_yy, S_xy.
@@ -91,7 +61,7 @@ __global__ __launch_bounds__(PL_T) void phys_loss_fwd_kernel(
 #pragma unroll
   for (int k = 0; k < 8; ++k) s[k] = 0.0;
   for (int i = n0 + (int)threadIdx.x; i < n1; i += PL_T) {   // a graph without rows: every sum stays 0
-    const Row a = load_z(y, i, off);
+    const Sym3 a = load_z(y, i, off);
     if (bvec) {
       const float bl = blen[i];
       if (labels[i] == -1 && bl > 0.f) {   // false for a NaN length
@@ -102,11 +72,11 @@ __global__ __launch_bounds__(PL_T) void phys_loss_fwd_kernel(
       }
     }
     if (rowptr) {
-      for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
-        if (eattr[perm[k]] != 0.f) continue;   // a periodic connection has length exactly 0
+      for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {   // the periodic connections of i (pdg_sym3.hpp)
+        if (eattr[perm[k]] != 0.f) continue;
         const int j = src[k];
-        if (j < n0 || j >= n1) continue;       // an edge never leaves its graph; one that does is not read
-        const Row b = load_z(y, j, off);
+        if (j < n0 || j >= n1) continue;
+        const Sym3 b = load_z(y, j, off);
         const double dx = a.x - b.x, dy = a.y - b.y, dxy = a.xy - b.xy;
         s[2] += dx * dx + dy * dy + dxy * dxy;
         s[3] += 1.0;
@@ -122,7 +92,7 @@ __global__ __launch_bounds__(PL_T) void phys_loss_fwd_kernel(
       }
     }
   }
-  pl_block_sum<8>(s, red);
+  block_sum_k<8>(s, red);
   if (threadIdx.x == 0) {
     double* row = table + (size_t)g * PL_COLS;
     const double L = s[0], T2 = s[1], P2 = 0.5 * s[2], np = 0.5 * s[3], W = s[4];
@@ -155,15 +125,6 @@ __global__ __launch_bounds__(PL_T) void phys_loss_fwd_kernel(
   }
 }
 
-__device__ __forceinline__ int graph_of(const int* __restrict__ ptr, int B, int node) {
-  int lo = 0, hi = B;  // ptr[lo] <= node < ptr[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= node) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(PL_CT) void phys_loss_bwd_kernel(
     int B, const int* __restrict__ ptr, int N, const float* __restrict__ y, const float* __restrict__ affine,
     const float* __restrict__ bvec, const float* __restrict__ blen, const int64_t* __restrict__ labels,
@@ -186,29 +147,21 @@ __global__ __launch_bounds__(PL_CT) void phys_loss_bwd_kernel(
   const bool on_m = wm != 0.f && area && D > 0.0 && W > 0.0;
   double o[3] = {0.0, 0.0, 0.0};   // a row that takes no part: exact zeros
   if (on_t || on_p || on_m) {
-    const Row a = load_z(y, i, off);
+    const Sym3 a = load_z(y, i, off);
     if (on_t) {
       const float bl = blen[i];
-      if (labels[i] == -1 && bl > 0.f) {
-        const double ct = (double)wt / L;
-        const double mx = (double)bvec[(size_t)i * 2], my = (double)bvec[(size_t)i * 2 + 1];
-        double fx, fy;
-        force(a, mx, my, fx, fy);
-        const double c = 2.0 / (double)bl;
-        o[0] = ct * (c * (fx * mx));
-        o[1] = ct * (c * (fy * my));
-        o[2] = ct * (c * (fx * my + fy * mx));
-      }
+      if (labels[i] == -1 && bl > 0.f)
+        traction_grad(a, (double)bvec[(size_t)i * 2], (double)bvec[(size_t)i * 2 + 1], bl, (double)wt / L, o);
     }
     if (on_p) {
       const double cp = (double)wp / np;
       double d[3] = {0.0, 0.0, 0.0};
       int cnt = 0;
-      for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {   // the periodic connections of i (pdg_sym3.hpp)
         if (eattr[perm[k]] != 0.f) continue;
         const int j = src[k];
         if (j < n0 || j >= n1) continue;
-        const Row b = load_z(y, j, off);
+        const Sym3 b = load_z(y, j, off);
         d[0] += a.x - b.x;
         d[1] += a.y - b.y;
         d[2] += a.xy - b.xy;
@@ -234,7 +187,7 @@ __global__ __launch_bounds__(PL_CT) void phys_loss_bwd_kernel(
   }
 }
 
-// pdg_loss.hip's loss_reduce_kernel with the three physics sums (its block_sum_k is pl_block_sum).
+// pdg_loss.hip's loss_reduce_kernel with the three physics sums.
 __global__ void loss_reduce_phys_kernel(int B, const float* __restrict__ ln, const float* __restrict__ ld,
                                         const float* __restrict__ lp, float sn, float sdv,
                                         const float* __restrict__ sp, const float* __restrict__ nz,
@@ -248,7 +201,7 @@ __global__ void loss_reduce_phys_kernel(int B, const float* __restrict__ ln, con
 #pragma unroll
       for (int k = 0; k < 3; ++k) v[2 + k] += (double)lp[(size_t)g * 3 + k];
   }
-  pl_block_sum<5>(v, red);
+  block_sum_k<5>(v, red);
   if (threadIdx.x == 0) {
 #pragma clang fp contract(off)
     const float fn = (float)v[0] * sn;
@@ -271,17 +224,12 @@ __global__ void loss_reduce_phys_kernel(int B, const float* __restrict__ ln, con
   }
 }
 
-int all_or_none(const void* a, const void* b, const void* c, const void* d, int n) {
-  const int given = (a != nullptr) + (b != nullptr) + (c != nullptr) + (n > 3 && d != nullptr);
-  return given == 0 || given == n;
-}
-
 }  // namespace
 
 #define PL_CHECK_GROUPS(name)                                                                                       \
-  PDG_CHECK_ARG(all_or_none(bvec, blen, labels, nullptr, 3),                                                        \
+  PDG_CHECK_ARG(all_or_none({bvec, blen, labels}),                                                                  \
                 name ": partial boundary arguments (bvec, blen and labels are given together or all NULL)");        \
-  PDG_CHECK_ARG(all_or_none(rowptr_dst, src, perm, edge_attr, 4),                                                   \
+  PDG_CHECK_ARG(all_or_none({rowptr_dst, src, perm, edge_attr}),                                                    \
                 name ": partial edge arguments (rowptr_dst, src, perm and edge_attr are given together or all "     \
                      "NULL)");                                                                                      \
   PDG_CHECK_ARG((area != nullptr) == (target != nullptr) && (area != nullptr || denom == nullptr),                  \

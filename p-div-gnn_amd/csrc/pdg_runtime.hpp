@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../include/pdivgnn.h"
@@ -33,6 +34,13 @@ constexpr int MAX_BLOCKS = 2048;
   } while (0)
 
 #define PDG_ALIGNED(p) ((((uintptr_t)(p)) & 15u) == 0)
+
+// An optional group of pointer arguments: given together or all NULL.
+inline bool all_or_none(std::initializer_list<const void*> group) {
+  size_t given = 0;
+  for (const void* p : group) given += p != nullptr;
+  return given == 0 || given == group.size();
+}
 
 // f(std::bool_constant<b>{}...) for run-time bools: a launcher's generic lambda names its kernel once,
 // kernel<decltype(R)::value, ...>, and every combination of the template bools is instantiated.

@@ -16,7 +16,7 @@
 // (~ 32 u d^2 / |A|, far below TOL = 2^-40 for any cell a mesher produces) as much room again.  Count (atomics
 // on the bin counters), pdg_scan.hpp's exclusive scan, fill (atomics claim the slots).  The order of the cells
 // inside a bin is whatever the atomics gave; nothing reads it as an order (below).  Cells of zero area (det == 0
-// with pdg_meshfields.hip's det) and cells with a vertex index outside [0, n_nodes) enter no bin and are counted
+// with pdg_cell.hpp's det, the mesh fields') and cells with a vertex index outside [0, n_nodes) enter no bin and are counted
 // in info.  The total is kept in 64 bits; a slot is written only when its position is inside [0, capacity).
 //
 // Location.  Triangles: w_k = [(p_k+1 - p) x (p_k+2 - p)] / det, signed sub-area over signed area, so either
@@ -49,6 +49,7 @@
 #include <cfloat>
 
 #include "pdg_bbox.hpp"
+#include "pdg_cell.hpp"
 #include "pdg_group.hpp"
 #include "pdg_runtime.hpp"
 #include "pdg_scan.hpp"
@@ -125,42 +126,6 @@ __device__ __forceinline__ int bin_of(double x, double x0, double inv, int g) {
   if (!(f >= 0.0)) return 0;
   if (f >= (double)g) return g - 1;
   return (int)f;
-}
-
-template <int NV>
-__device__ __forceinline__ bool in_range(const int64_t* __restrict__ t, int n) {
-  bool ok = true;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) ok = ok && t[v] >= 0 && t[v] < n;
-  return ok;
-}
-
-template <int NV>
-struct Cell {
-  double x[NV], y[NV], det;
-};
-
-// pdg_meshfields.hip's det = 2 * signed area: (xb - xa)(yc - ya) - (xc - xa)(yb - ya) of a triangle, the diagonals'
-// cross product (xc - xa)(yd - yb) - (xd - xb)(yc - ya) of a quad.
-template <int NV>
-__device__ __forceinline__ Cell<NV> cell_of(const float* __restrict__ p, int dim, const int64_t* __restrict__ t) {
-#pragma clang fp contract(off)
-  Cell<NV> q;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    q.x[v] = p[(size_t)t[v] * dim];
-    q.y[v] = p[(size_t)t[v] * dim + 1];
-  }
-  if constexpr (NV == 3) {
-    const double m0 = (q.x[1] - q.x[0]) * (q.y[2] - q.y[0]);
-    const double m1 = (q.x[2] - q.x[0]) * (q.y[1] - q.y[0]);
-    q.det = m0 - m1;
-  } else {
-    const double m0 = (q.x[2] - q.x[0]) * (q.y[3] - q.y[1]);
-    const double m1 = (q.x[3] - q.x[1]) * (q.y[2] - q.y[0]);
-    q.det = m0 - m1;
-  }
-  return q;
 }
 
 enum { CELL_OK = 0, CELL_DEGENERATE = 1, CELL_RANGE = 2 };
