@@ -1157,6 +1157,74 @@ int pdg_fem_stress(int n_graphs, int n_cases, const int* ptr, const int* fptr, i
                    const double* elem, const double* strains, const double* ut, double young, double poisson,
                    int nodal, float* stress, float* strain, double* sums, void* stream);
 
+/* ---------------------------------------------------------------- Hyperelastic FEM targets */
+/* The periodic cell problem of a compressible neo-Hookean material in plane strain under a finite mean deformation
+ * (pdg_hyper.hip), on the meshes, the plan arrays and the element table of "FEM targets" above (pdg_fem_elements):
+ *   u(X) = (Fbar - I) X + ut(X), ut periodic; per element F = Fbar + grad ut, F3 = diag(F, 1), I1 = tr(F^T F) + 1,
+ *   J = det F,  W = mu / 2 (J^(-2/3) I1 - 3) + U(J),
+ *   volumetric 0 ("log"):       U = kappa (J ln J - J + 1),  U' = kappa ln J,
+ *   volumetric 1 ("quadratic"): U = kappa / 2 (J - 1)^2,
+ *   P = mu J^(-2/3) (F - I1 / 3 F^-T) + U'(J) J F^-T (first Piola-Kirchhoff, 2 x 2), A = dP/dF (4 x 4, symmetric, on
+ *   (F00, F01, F10, F11)), sigma = P F^T / J (Cauchy).
+ * fbar (n_graphs, n_cases, 4) fp64 = F00, F01, F10, F11 of every problem.  Sizes, null pointers (all but the stream),
+ * the material (mu, kappa finite and > 0, volumetric 0 or 1), rtol and eta in (0, 1), n_steps in [1, 10000] and the
+ * scratch size are refused on the host before any HIP call.  Every index read on the device is checked against its
+ * array before it addresses anything; an item that fails is skipped.  Every expression is evaluated as written,
+ * contraction off.
+ *
+ * pdg_hyper_solve.  The balance r_v = -sum area P_e g_c = 0 at every periodic representative, with ut of zero mean
+ * over the representatives.  One persistent workgroup of 1024 threads per (graph, load case), grid n_graphs x n_cases:
+ * thread t owns the representatives t, t + 1024, ... and the faces fptr[g] + t, fptr[g] + t + 1024, ... of its
+ * graph; every row is gathered by its owner in ascending item order (no scatter), every sum is an fp64 block sum
+ * folded in a fixed order, no float atomics, nothing allocated, no memset: a graph gets bitwise the same rows alone
+ * and inside any batch, and it can be captured.  For each of n_steps equal increments Fbar(t) = I + t (Fbar - I),
+ * t = step / n_steps, Newton iterations, each of
+ *   element pass   F_e, P_e, A_e of the graph's faces into scratch (14 doubles a face), and Phi = sum area W(F_e); an
+ *                  element with J_e <= 0 or a value that is not finite is counted through the same block sum;
+ *   row pass       r_v, f_abs (the same sums of the terms' absolute values) and the diagonal of the tangent;
+ *   convergence    |r|_2 <= rtol |f_abs|_2: scale-free; a plate without a hole converges with no iteration, ut = 0;
+ *   inner solve    A d = r by the Jacobi-preconditioned conjugate gradients of pdg_fem_solve (the mean over the
+ *                  representatives taken off z) from d = 0, the tangent applied from the stored A_e, until
+ *                  |r_k|_2 <= eta |r_0|_2 or max_pcg iterations (clamped to [1, 100000]); on p^T A p <= 0 it stops
+ *                  with the iterate so far, or with the preconditioned residual when there is none yet: a descent
+ *                  direction, a truncation and not a failure;
+ *   backtracking   alpha = 1, 1/2, .. 2^-10: the step is accepted when no element has J_e <= 0 and
+ *                  Phi(x + alpha d) <= Phi(x) - 1e-4 alpha r.d, the two rounded sums compared with an allowance of
+ *                  32 ulp of the sum of area |terms of W| (what cancels inside W is rounding, not an increase).
+ * Every decision is taken from block sums every thread holds alike, and every loop is capped, so no input makes the
+ * workgroup spin.  Status (pdg_fem_solve's codes; 1 is not used): 0 CONVERGED; 2 MAX_ITER, a load step's Newton
+ * iteration reached max_newton (per step, clamped to [0, 1000]); 3 BREAKDOWN, an exhausted line search, a sum that
+ * is not finite, or a load step that starts with an inverted element.  MAX_ITER and BREAKDOWN return the current
+ * iterate; when a sum was not finite ut is NaN.
+ * ut (n_cases, n_nodes, 2) fp64: the periodic part at every node (an image holds its representative's row).
+ * table (n_graphs, n_cases, 6) fp64 = load steps completed, Newton iterations (all steps), conjugate-gradient
+ * iterations (all steps), the last row pass's |f_abs|_2, the true final relative residual |r|_2 / |f_abs|_2
+ * recomputed from the returned ut under the whole load (NaN when it holds an inverted element), status.  An empty
+ * graph (ptr[g + 1] == ptr[g]) gets a NaN table row and nothing else is written for it.
+ * scratch: seven 2 n_nodes fp64 vectors and 14 doubles per face, per load case;
+ * pdg_hyper_solve_scratch_bytes(n_nodes, n_faces, n_cases) bytes (< 0 unless 0 < n_nodes, n_faces < 2^29 and
+ * 0 < n_cases <= 64).
+ *
+ * pdg_hyper_stress.  From F_e = Fbar + grad ut in fp64:
+ *   stress (n_cases, n_nodes, 3) fp32: the Cauchy stress xx, yy, xy; strain, the same shape: the logarithmic strain
+ *     1/2 ln(F F^T) as xx, yy, 2 xy; each the average over the node's own corners (not its images') of the incident
+ *     elements' values, weighted by the deformed area area J_e (nodal == 0) or unweighted (nodal == 1), the terms
+ *     added in ascending item order and rounded once; 0 for a node of no face;
+ *   sums (n_graphs, n_cases, 10) fp64 = sum area J sigma (xx, yy, xy), sum area P (00, 01, 10, 11), sum area J (the
+ *     deformed material area), the material area, the bounding box's area of the undeformed points, each a block sum
+ *     in a fixed order; NaN for an empty graph.
+ * Two kernel launches, nothing else: it can be captured. */
+long pdg_hyper_solve_scratch_bytes(int n_nodes, int n_faces, int n_cases);
+int pdg_hyper_solve(int n_graphs, int n_cases, const int* ptr, const int* fptr, int n_nodes, int n_faces,
+                    const int* rverts, const int* rep, const int* item_rowptr, const int* item, const double* elem,
+                    const double* fbar, double mu, double kappa, int volumetric, double rtol, int n_steps,
+                    int max_newton, double eta, int max_pcg, double* ut, double* table, void* scratch,
+                    long scratch_bytes, void* stream);
+int pdg_hyper_stress(int n_graphs, int n_cases, const int* ptr, const int* fptr, int n_nodes, const float* points,
+                     int dim, int n_faces, const int* verts, const int* rep, const int* item_rowptr, const int* item,
+                     const double* elem, const double* fbar, const double* ut, double mu, double kappa,
+                     int volumetric, int nodal, float* stress, float* strain, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

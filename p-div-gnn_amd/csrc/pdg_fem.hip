@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "pdg_common.hpp"
+#include "pdg_femmesh.hpp"
 #include "pdg_reduce.hpp"
 #include "pdg_runtime.hpp"
 
@@ -77,35 +78,7 @@ __global__ __launch_bounds__(256) void fem_elements_kernel(int n_nodes, const fl
 }
 
 // ------------------------------------------------------------------------------------------------------- solver
-struct Mesh {
-  const float* points;
-  int dim;
-  int n_nodes, n_faces;
-  const int* verts;    // (3 F) node of every corner
-  const int* rverts;   // (3 F) its periodic representative
-  const int* rep;      // (N)
-  const int* rowptr;   // (N + 1) items of a representative: the corners that are it or an image of it
-  const int* item;     // (3 F) 3 face + corner
-  const double* elem;  // (F, 8)
-  int n0, n1;          // the graph's node segment
-};
-
-// The first and one past the last item of row v, clamped to the item array.
-__device__ __forceinline__ void row_range(const Mesh& m, int v, int& j0, int& j1) {
-  j0 = m.rowptr[v];
-  j1 = m.rowptr[v + 1];
-  if (j0 < 0) j0 = 0;
-  if (j1 > 3 * m.n_faces) j1 = 3 * m.n_faces;
-}
-
-// The face and corner of item j; false for an item outside the mesh (it is skipped before anything is addressed).
-__device__ __forceinline__ bool item_of(const Mesh& m, int j, int& f, int& c) {
-  const unsigned it = (unsigned)m.item[j];
-  if (it >= 3u * (unsigned)m.n_faces) return false;
-  f = (int)(it / 3u);
-  c = (int)(it - 3u * (unsigned)f);
-  return true;
-}
+// Mesh, row_range and item_of: pdg_femmesh.hpp, shared with pdg_hyper.hip.
 
 // area B_c^T sigma: the force of the element's stress at its corner c.
 __device__ __forceinline__ void corner_force(const double* e, int c, const double (&sg)[3], double& fx, double& fy) {
