@@ -1225,6 +1225,49 @@ int pdg_hyper_stress(int n_graphs, int n_cases, const int* ptr, const int* fptr,
                      const double* elem, const double* fbar, const double* ut, double mu, double kappa,
                      int volumetric, int nodal, float* stress, float* strain, double* sums, void* stream);
 
+/* ---------------------------------------------------------------- Q1 FEM targets */
+/* The linear cell problem of "FEM targets" above on bilinear (Q1) quads (pdg_femq1.hip): the same material, load
+ * cases, arrays and checks, argument for argument, with four corners a face: verts, rverts and item hold 4 n_faces
+ * entries, an item is 4 face + corner, and a face's vertices run around it in either orientation.  The integrals are
+ * the 2 x 2 Gauss rule's, xi, eta = +-1 / sqrt(3), which is exact for the stiffness of a parallelogram; Gauss point g
+ * is the one nearest corner g of the face's own vertex order (reference corners (-1, -1), (1, -1), (1, 1), (-1, 1)).
+ * Host-side refusals, their order and their messages are those of the triangle calls.
+ *
+ * pdg_femq1_elements.  elem (n_faces, 36) fp64: for each Gauss point g, at 9 g, det J, dN/dx[4], dN/dy[4], in fp64
+ * from the fp32 coordinates, every expression as written, contraction off; the gradients use the signed inverse of J
+ * and every weight is |det J|, so a clockwise quad (all four det J < 0) is accepted.  *status (cleared here): 1 a
+ * face whose four det J are not all strictly of one sign (a zero, a non-convex quad, a bow-tie: launch no solve),
+ * 2 a vertex outside [0, n_nodes) (the face's row is NaN).
+ *
+ * pdg_femq1_solve.  pdg_fem_solve's contract with K = sum_f sum_g |det J_g| B(g)^T C B(g): one persistent workgroup
+ * of 1024 threads per (graph, load case), thread t owning the representatives t, t + 1024, ...; row v is gathered by
+ * its owner over the items of v in ascending order, each item's corner force the sum over g = 0..3, in that order, of
+ * |det J_g| B_c(g)^T C B(g) u (no scatter); Jacobi preconditioner, zero mean over the representatives; b_abs sums the
+ * items' absolute corner forces; the noise rule, the clamp of max_iter to [0, 100000], the breakdown rule, the true
+ * final relative residual, the table row, the NaN row of an empty graph and the status codes are pdg_fem_solve's.
+ * scratch: pdg_femq1_solve_scratch_bytes(n_nodes, n_cases) bytes, x, r, p, A p, 1 / diag A: 80 bytes per node and
+ * case (< 0 unless 0 < n_nodes < 2^29 and 0 < n_cases <= 64).  No float atomics, nothing allocated, no memset: a
+ * graph gets bitwise the same rows alone and inside any batch, and it can be captured.
+ *
+ * pdg_femq1_stress.  From u = eps x + ut in fp64:
+ *   stress, strain (n_cases, n_nodes, 3) fp32: the average over the node's own corners (not its images') of the
+ *     incident faces' values at the Gauss point nearest that corner, weighted by that point's |det J| (nodal == 0) or
+ *     unweighted (nodal == 1), the terms added in ascending item order and rounded once; 0 for a node of no face;
+ *   sums (n_graphs, n_cases, 8) fp64, pdg_fem_stress's layout: sum_f sum_g |det J_g| sigma_g (3), the same of eps
+ *     (3), the material area sum |det J_g|, the bounding box's area; NaN for an empty graph.
+ * Two kernel launches, nothing else: it can be captured. */
+int pdg_femq1_elements(int n_nodes, const float* points, int dim, int n_faces, const int* verts, double* elem,
+                       int* status, void* stream);
+long pdg_femq1_solve_scratch_bytes(int n_nodes, int n_cases);
+int pdg_femq1_solve(int n_graphs, int n_cases, const int* ptr, int n_nodes, const float* points, int dim, int n_faces,
+                    const int* verts, const int* rverts, const int* rep, const int* item_rowptr, const int* item,
+                    const double* elem, const double* strains, double young, double poisson, double rtol,
+                    int max_iter, double* ut, double* table, void* scratch, long scratch_bytes, void* stream);
+int pdg_femq1_stress(int n_graphs, int n_cases, const int* ptr, const int* fptr, int n_nodes, const float* points,
+                     int dim, int n_faces, const int* verts, const int* rep, const int* item_rowptr, const int* item,
+                     const double* elem, const double* strains, const double* ut, double young, double poisson,
+                     int nodal, float* stress, float* strain, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

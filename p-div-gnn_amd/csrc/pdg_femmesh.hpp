@@ -36,4 +36,21 @@ __device__ __forceinline__ bool item_of(const Mesh& m, int j, int& f, int& c) {
   return true;
 }
 
+// The same two for a mesh of quads (pdg_femq1.hip): verts, rverts and item hold 4 F entries, an item is
+// 4 face + corner, elem is (F, 36).
+__device__ __forceinline__ void row_range4(const Mesh& m, int v, int& j0, int& j1) {
+  j0 = m.rowptr[v];
+  j1 = m.rowptr[v + 1];
+  if (j0 < 0) j0 = 0;
+  if (j1 > 4 * m.n_faces) j1 = 4 * m.n_faces;
+}
+
+__device__ __forceinline__ bool item_of4(const Mesh& m, int j, int& f, int& c) {
+  const unsigned it = (unsigned)m.item[j];
+  if (it >= 4u * (unsigned)m.n_faces) return false;
+  f = (int)(it >> 2);
+  c = (int)(it & 3u);
+  return true;
+}
+
 }  // namespace pdg
