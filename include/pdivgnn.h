@@ -1268,6 +1268,65 @@ int pdg_femq1_stress(int n_graphs, int n_cases, const int* ptr, const int* fptr,
                      const double* elem, const double* strains, const double* ut, double young, double poisson,
                      int nodal, float* stress, float* strain, double* sums, void* stream);
 
+/* ---------------------------------------------------------------- Q1 hyperelastic FEM targets */
+/* The neo-Hookean cell problem of "Hyperelastic FEM targets" above on the bilinear quads of "Q1 FEM targets"
+ * (pdg_hyperq1.hip): the same law, load cases, solver, outputs and checks, argument for argument, on the plan arrays
+ * of a quad mesh (verts, rverts and item hold 4 n_faces entries, an item is 4 face + corner) and the element table of
+ * pdg_femq1_elements, elem (n_faces, 36) fp64.  The law is evaluated at the four Gauss points of every face:
+ *   F_g = Fbar + sum_k ut_k (x) grad N_k(g),  w_g = |det J_g|,  P_g, A_g as above,  Phi = sum_f sum_g w_g W(F_g).
+ * Host-side refusals, their order and their messages are those of pdg_hyper_solve and pdg_hyper_stress.  Every index
+ * read on the device is checked against its array before it addresses anything; an item that fails is skipped.  Every
+ * expression is evaluated as written, contraction off; the constitutive code is pdg_hyper.hip's (pdg_neohooke.hpp).
+ *
+ * pdg_hyperq1_solve.  The balance r_v = -sum_items sum_g w_g P_g grad N_c(g) = 0 at every periodic representative,
+ * ut of zero mean over the representatives.  One persistent workgroup of 512 threads per (graph, load case), grid
+ * n_graphs x n_cases (512, not the triangle solver's 1024: four Gauss points a face want more than the 128 registers
+ * a thread of 1024 has, and nothing may spill inside the solver's loops): thread t owns the representatives t,
+ * t + 512, ... and the faces fptr[g] + t, fptr[g] + t + 512, ... of its graph; every row is gathered by its owner in
+ * ascending item order, g = 0..3 inside an item (no scatter), every sum is an fp64 block sum folded in a fixed order,
+ * no float atomics, nothing allocated, no memset: a graph gets bitwise the same rows alone and inside any batch, and
+ * it can be captured.  The solver is pdg_hyper_solve's, word for word: n_steps equal increments of Fbar - I, Newton
+ * with the backtracking line search (alpha = 1, 1/2, .. 2^-10, the Armijo constant 1e-4, the allowance of 32 ulp of
+ * the sum of w_g |terms of W|), the inner Jacobi-preconditioned conjugate gradients with the mean taken off z, the
+ * truncation at eta and a direction of no positive curvature treated as a truncation; convergence at
+ * |r|_2 <= rtol |f_abs|_2, f_abs the same sums as r of the terms' absolute values, one term a (item, Gauss point);
+ * the same caps (n_steps <= 10000, max_newton clamped to [0, 1000] per step, max_pcg to [1, 100000], 11 trial
+ * steps), so no input makes the workgroup spin; the same status codes and the same table (n_graphs, n_cases, 6), its
+ * true final relative residual recomputed from the returned ut under the whole load; an empty graph gets a NaN table
+ * row and nothing else is written for it.  What differs from triangles:
+ *   element pass   P_g (4) and A_g (10) of every Gauss point into scratch, 56 doubles a face; a face counts as
+ *                  inverted when any of its four J_g is <= 0 or not finite, counted through the same block sum, and
+ *                  then stores zeros at all four points: it adds no force and no stiffness;
+ *   row passes     the diagonal and the tangent-times-vector row use dF_g = sum_k q_k (x) grad N_k(g) from the
+ *                  face's four representatives (rverts);
+ *   a plate without a hole converges with no iteration and ut = 0 on any mesh of convex quads: the 2 x 2 rule
+ *                  integrates grad N det J exactly, so the exact residual of a uniform P is 0.
+ * scratch: seven 2 n_nodes fp64 vectors and 56 doubles per face, per load case;
+ * pdg_hyperq1_solve_scratch_bytes(n_nodes, n_faces, n_cases) bytes (< 0 unless 0 < n_nodes, n_faces < 2^29 and
+ * 0 < n_cases <= 64: pdg_hyper_solve_scratch_bytes' ranges).
+ *
+ * pdg_hyperq1_stress.  pdg_femq1_stress's nodal rule with pdg_hyper_stress's quantities, from F_g in fp64:
+ *   stress (n_cases, n_nodes, 3) fp32: the Cauchy stress xx, yy, xy; strain, the same shape: the logarithmic strain
+ *     1/2 ln(F F^T) as xx, yy, 2 xy; each the average over the node's own corners (not its images') of the incident
+ *     faces' values at the Gauss point nearest that corner, weighted by that point's deformed weight w_g J_g
+ *     (nodal == 0) or unweighted (nodal == 1), the terms added in ascending item order and rounded once; 0 for a
+ *     node of no face;
+ *   sums (n_graphs, n_cases, 10) fp64, pdg_hyper_stress's layout with sum_f sum_g w_g .. in place of area ..:
+ *     sum w_g J_g sigma_g (xx, yy, xy), sum w_g P_g (00, 01, 10, 11), sum w_g J_g (the deformed material area), the
+ *     material area sum w_g, the bounding box's area of the undeformed points; NaN for an empty graph.
+ * Two kernel launches, nothing else: it can be captured. */
+long pdg_hyperq1_solve_scratch_bytes(int n_nodes, int n_faces, int n_cases);
+int pdg_hyperq1_solve(int n_graphs, int n_cases, const int* ptr, const int* fptr, int n_nodes, int n_faces,
+                      const int* rverts, const int* rep, const int* item_rowptr, const int* item, const double* elem,
+                      const double* fbar, double mu, double kappa, int volumetric, double rtol, int n_steps,
+                      int max_newton, double eta, int max_pcg, double* ut, double* table, void* scratch,
+                      long scratch_bytes, void* stream);
+int pdg_hyperq1_stress(int n_graphs, int n_cases, const int* ptr, const int* fptr, int n_nodes, const float* points,
+                       int dim, int n_faces, const int* verts, const int* rep, const int* item_rowptr,
+                       const int* item, const double* elem, const double* fbar, const double* ut, double mu,
+                       double kappa, int volumetric, int nodal, float* stress, float* strain, double* sums,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

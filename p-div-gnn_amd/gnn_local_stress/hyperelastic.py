@@ -25,7 +25,7 @@ Jacobi-preconditioned conjugate gradients inside) and ``pdg_hyper_stress`` (noda
 plate without a hole is ``CONVERGED`` with no iteration and ``ut = 0``).  Nothing is read back after the solve: a
 caller who needs convergence checked reads ``table[..., 5]``.
 
-Triangles only; CPU tensors raise (the CPU restatement is test-only, tests/hyper_ref.py).
+Triangles only (quad meshes go to ``gnn_local_stress.hyperelastic_q1``); CPU tensors raise (the CPU restatement is test-only, tests/hyper_ref.py).
 """
 from __future__ import annotations
 

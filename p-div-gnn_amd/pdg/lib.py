@@ -173,6 +173,11 @@ SIGNATURES: dict[str, list] = {
     "pdg_femq1_solve_scratch_bytes": [I, I],
     "pdg_femq1_solve": [I, I, P, I, P, I, I] + [P] * 7 + [c_double, c_double, c_double, I, P, P, P, ctypes.c_long, P],
     "pdg_femq1_stress": [I, I, P, P, I, P, I, I] + [P] * 7 + [c_double, c_double, I, P, P, P, P],
+    # Q1 hyperelastic FEM targets (csrc/pdg_hyperq1.hip): the triangle calls' arguments
+    "pdg_hyperq1_solve_scratch_bytes": [I, I, I],
+    "pdg_hyperq1_solve": [I, I, P, P, I, I] + [P] * 6 + [c_double, c_double, I, c_double, I, I, c_double, I, P, P, P,
+                                                          ctypes.c_long, P],
+    "pdg_hyperq1_stress": [I, I, P, P, I, P, I, I] + [P] * 7 + [c_double, c_double, I, I, P, P, P, P],
 }
 # the entry points that return a value, not a status: called as they are (no error check, not counted in
 # lib.calls, not passed to lib.hook)
@@ -184,6 +189,7 @@ _RESTYPES = {"pdg_last_error": ctypes.c_char_p, "pdg_source_hash": ctypes.c_char
              "pdg_cell_bins_scratch_bytes": ctypes.c_long, "pdg_sample_csr_scratch_bytes": ctypes.c_long,
              "pdg_equilibrate_scratch_bytes": ctypes.c_long, "pdg_fem_solve_scratch_bytes": ctypes.c_long,
              "pdg_hyper_solve_scratch_bytes": ctypes.c_long, "pdg_femq1_solve_scratch_bytes": ctypes.c_long,
+             "pdg_hyperq1_solve_scratch_bytes": ctypes.c_long,
              "pdg_version": c_int, "pdg_max_blocks": c_int, "pdg_wgrad_slabs_per_cu": c_int, "pdg_pq_layout": c_int}
 
 LN_STAT_BYTES = 40   # sizeof(pdg_ln_stat)
